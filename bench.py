@@ -2,8 +2,15 @@
 """Benchmark: DeiT-S/16 224px bf16 data-parallel training on MI355X (BASELINE.json configs[1]
 at N=1; the same per-GPU workload at N>1, weak scaling) with the fused HIP attention on the hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+ms_per_step, config, e2e): nothing else touches the GPU or the host cores.  ``--full`` adds every
+other measurement described below (roofline, attention, attention_headline, cpu_baseline), each a
+run of its own after the timed region.  ``--dump-outputs DIR`` writes, right after the timed steps,
+what the last timed step computed (dump_outputs below) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 One process per GPU; each rank holds 128 synthetic N(0,1) images (fed as the reference's train step
 receives them: HWCN fp32, train.py:80-81) + uniform labels, resident in HBM.  The step is forward,
@@ -17,6 +24,8 @@ before AdamW).  ``--world1-rccl`` runs that collective path at N=1 with a one-ra
 by a barrier + device synchronisation on both sides; the max elapsed time over ranks is used.
 Rank 0 prints ONE JSON line:
   value        = whole-job training images/s (all ranks)
+  ms_per_step  = elapsed time of the timed region / K, milliseconds
+and with ``--full`` also:
   roofline     = the fused attention op of this workload: one call = 2 launches (attn_fwd2 +
                  the single-pass attn_bwd3 at DeiT-S), timed with HIP events on the launch stream
                  around a HIP graph of 10 back-to-back calls at the workload's layer shape (packed
@@ -244,6 +253,34 @@ def headline(dev, iters=20, reps=10, f32=False):
             "timing": f"HIP graphs of {reps} launches, median of {iters} replays", "roofline": r}
 
 
+DUMP_MAX_ELEMS = 4 * 2 ** 20   # per array: 16 MB of float32, so loss + params + grads stay well under 64 MB
+
+
+def dump_outputs(dirpath, step, loss):
+    """What the last timed step computed, as float32 ``<dirpath>/<name>.npy``:
+      loss   [1]  the value ``step(images, labels)`` returned
+      params      the parameters after the step's AdamW update, flattened in registration order
+      grads       the step's gradients (the flat fp32 buffer with its alignment padding, all-reduced
+                  at N > 1; the per-parameter gradients in registration order with --no-flat-grads)
+    An array longer than DUMP_MAX_ELEMS is cut to a fixed sample of that many elements (sorted
+    indices drawn with seed 0 from the array's length: the same elements on every run and build)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1),
+              "params": torch.cat([p.detach().reshape(-1) for p in step._params])}
+    if step.flat:
+        arrays["grads"] = step._flat
+    elif all(p.grad is not None for p in step._params):
+        arrays["grads"] = torch.cat([p.grad.detach().reshape(-1) for p in step._params])
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(dirpath, name + ".npy"), t.float().cpu().numpy())
+
+
 def step_label(step, use_graph):
     """What the timed step ran, named by the collective path that actually executed (train.py)."""
     if not (use_graph and step.graph):
@@ -259,6 +296,30 @@ def step_label(step, use_graph):
     return f"{base} + {coll[step.collective]}"
 
 
+def step_roofline(args, dev, ksum, is_cait, B, N, Hh, D, kf, kb):
+    """--full: (roofline entry, fwd ms, bwd ms) of the workload's dominant attention call."""
+    import torch
+    f_fwd, f_bwd, b_fwd, b_bwd = attn_work(B, N, N, Hh, D)
+    if is_cait:   # + the two H x H head mixes, fwd and bwd (SURVEY §8d)
+        f_fwd += 2 * 2.0 * B * Hh * Hh * N * N
+        f_bwd += 2 * 4.0 * B * Hh * Hh * N * N
+    ev_fwd_ms, ev_bwd_ms = ksum[kf]["mean_ms"], ksum[kb]["mean_ms"]
+    if is_cait:   # the talking-heads op: HIP events around its launches in the eager steps
+        fwd_ms, bwd_ms, how = ev_fwd_ms, ev_bwd_ms, "HIP events around each launch, eager steps after the timed region"
+    else:         # the same kernels at the workload's layer shape, replayed from a HIP graph
+        fwd_ms, bwd_ms = attn_graph_ms(dev, B, N, Hh, D, torch.bfloat16)
+        how = ("the workload's attention call ([B, N, 3, H, D] packed q/k/v) as a HIP graph of 10 launches "
+               "after the timed region, median of 20 replays (kernel time, as rocprofv3 reports it)")
+    is_deit_s = (args.model, args.img_size, B) == ("deit_s_patch16", 224, 128)
+    roof = roofline_entry(f_fwd + f_bwd, b_fwd + b_bwd, (fwd_ms + bwd_ms) / 1e3,
+                          load_traffic("deit_s") if is_deit_s else None)
+    roof["timing"] = how
+    roof["eager_step_events_ms_per_call"] = round(ev_fwd_ms + ev_bwd_ms, 4)
+    if is_deit_s and load_pmc("deit_s", "mfma_busy_frac") is not None:
+        roof["mfma_busy_frac"] = load_pmc("deit_s", "mfma_busy_frac")
+    return roof, fwd_ms, bwd_ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -269,9 +330,16 @@ def main():
                     help="ViT/DeiT (vit.MODEL_CONFIGS) or CaiT (cait.CAIT_CONFIGS, e.g. cait_s_24: configs[4])")
     ap.add_argument("--img-size", type=int, default=224,
                     help="input resolution (384 with --model vit_b_patch16 --batch 32: BASELINE configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-headline", action="store_true")
-    ap.add_argument("--profile", action="store_true", help="training loop only (for rocprofv3 runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the attention roofline and share of the step, the "
+                         "ViT-B/16@384 attention headlines (bf16, fp32) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, updated parameters, gradients; see "
+                         "dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-headline", action="store_true", help="--full without the attention headlines")
+    ap.add_argument("--profile", action="store_true",
+                    help="--full without the headlines and CPU baselines (for rocprofv3 runs)")
     ap.add_argument("--eager", action="store_true", help="N=1: eager step instead of the HIP-graph replay")
     ap.add_argument("--two-graphs", action="store_true",
                     help="N=1: the multi-rank step structure (forward+backward graph, the all-reduce point, AdamW "
@@ -296,6 +364,8 @@ def main():
                          "each bucket's all-reduce, CHANNELS workgroups hold CUs for the bucket's ring time at "
                          "BUSBW_GBPS (implies --world1-rccl; a diagnostic, never the bench line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed region divided by it)")
     if args.emulate_rccl:
         os.environ["SAE_EMULATE_RCCL"] = args.emulate_rccl
         args.world1_rccl = True
@@ -347,7 +417,7 @@ def main():
         images, labels = bufs
     torch.cuda.synchronize()
     timer = ops.KernelTimer()
-    if not use_graph:   # eager launches: the attention events sit inside the timed region
+    if args.full and not use_graph:   # eager launches: the attention events sit inside the timed region
         ops.set_kernel_timer(timer)
     if world > 1:
         dist.barrier()
@@ -363,7 +433,10 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ops.set_kernel_timer(None)
-    if use_graph:
+    final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:   # before anything else steps the model again
+        dump_outputs(args.dump_outputs, step, loss)
+    if args.full and use_graph:
         # graph replays carry no host-side events: time the same kernels with HIP events on their
         # launch stream over eager steps of the same workload, right after the timed region
         ops.set_kernel_timer(timer)
@@ -374,10 +447,7 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    final_loss = float(loss.item())
 
-    ksum = timer.summary()
-    timed_steps = TIMER_STEPS if use_graph else args.steps
     if is_cait:   # the dominant attention: the talking-heads self-attention trunk (no CLS token)
         L, _, Hh, C, _, _ = cait.CAIT_CONFIGS[args.model]
         N = (args.img_size // 16) ** 2
@@ -387,24 +457,8 @@ def main():
         N = (args.img_size // p) ** 2 + 1
         kf, kb = "attn_fwd", "attn_bwd"
     D = C // Hh
-    f_fwd, f_bwd, b_fwd, b_bwd = attn_work(B, N, N, Hh, D)
-    if is_cait:   # + the two H x H head mixes, fwd and bwd
-        f_fwd += 2 * 2.0 * B * Hh * Hh * N * N
-        f_bwd += 2 * 4.0 * B * Hh * Hh * N * N
-    ev_fwd_ms, ev_bwd_ms = ksum[kf]["mean_ms"], ksum[kb]["mean_ms"]
-    if is_cait:   # the talking-heads op: HIP events around its launches in the eager steps
-        fwd_ms, bwd_ms, how = ev_fwd_ms, ev_bwd_ms, "HIP events around each launch, eager steps after the timed region"
-    else:         # the same kernels at the workload's layer shape, replayed from a HIP graph
-        fwd_ms, bwd_ms = attn_graph_ms(dev, B, N, Hh, D, torch.bfloat16)
-        how = ("the workload's attention call ([B, N, 3, H, D] packed q/k/v) as a HIP graph of 10 launches "
-               "after the timed region, median of 20 replays (kernel time, as rocprofv3 reports it)")
-    is_deit_s = (args.model, args.img_size, B) == ("deit_s_patch16", 224, 128)
-    roof = roofline_entry(f_fwd + f_bwd, b_fwd + b_bwd, (fwd_ms + bwd_ms) / 1e3,
-                          load_traffic("deit_s") if is_deit_s else None)
-    roof["timing"] = how
-    roof["eager_step_events_ms_per_call"] = round(ev_fwd_ms + ev_bwd_ms, 4)
-    if is_deit_s and load_pmc("deit_s", "mfma_busy_frac") is not None:
-        roof["mfma_busy_frac"] = load_pmc("deit_s", "mfma_busy_frac")
+    if args.full:
+        roof, fwd_ms, bwd_ms = step_roofline(args, dev, timer.summary(), is_cait, B, N, Hh, D, kf, kb)
     img_s = B * world * args.steps / elapsed
     flop_img = 3 * (cait.cait_flops_per_image(args.model, args.img_size) if is_cait
                     else vit.vit_flops_per_image(args.model, args.img_size))
@@ -429,19 +483,21 @@ def main():
                                   "emulated_rccl": args.emulate_rccl or None,
                                   "buckets": len(getattr(step, "_buckets", [])), "bucket_cap_mb": args.bucket_mb}},
         "host_submit_ms_per_step": round(host / args.steps * 1e3, 3),
-        "roofline": roof,
-        "attention": {"kernel": kf.replace("_fwd", ""), "calls_per_step": ksum[kf]["launches"] // timed_steps,
-                      "fwd_ms": round(fwd_ms, 4), "bwd_ms": round(bwd_ms, 4), "tflops": roof["tflops"],
-                      "share_of_step": round((fwd_ms + bwd_ms) * ksum[kf]["launches"] / timed_steps
-                                             / (elapsed / args.steps * 1e3), 4)},
-        "e2e": {"train_flop_per_img": flop_img, "tflops": round(img_s * flop_img / 1e12, 1),
-                "mfma_frac": round(img_s * flop_img / 1e12 / (world * PEAK_BF16_TFLOPS), 4),
-                "final_loss": round(final_loss, 4)},
     }
-    if not args.profile and not args.no_headline:
+    if args.full:
+        calls = timer.summary()[kf]["launches"] / (TIMER_STEPS if use_graph else args.steps)
+        out["roofline"] = roof
+        out["attention"] = {"kernel": kf.replace("_fwd", ""), "calls_per_step": int(calls),
+                            "fwd_ms": round(fwd_ms, 4), "bwd_ms": round(bwd_ms, 4), "tflops": roof["tflops"],
+                            "share_of_step": round((fwd_ms + bwd_ms) * calls / (elapsed / args.steps * 1e3), 4)}
+    out["e2e"] = {"train_flop_per_img": flop_img, "tflops": round(img_s * flop_img / 1e12, 1),
+                  "mfma_frac": round(img_s * flop_img / 1e12 / (world * PEAK_BF16_TFLOPS), 4),
+                  "final_loss": round(final_loss, 4)}
+    if args.full and not args.profile and not args.no_headline:
         out["attention_headline"] = headline(dev)
         out["attention_headline_f32"] = headline(dev, iters=5, reps=3, f32=True)
-    if not args.profile and not args.no_cpu_baseline and world == 1 and args.img_size == 224 and not is_cait:
+    if (args.full and not args.profile and not args.no_cpu_baseline and world == 1 and args.img_size == 224
+            and not is_cait):
         out["cpu_baseline"] = cpu_baseline(args.model)
     os.write(out_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
