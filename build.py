@@ -3,10 +3,15 @@
 
 Usage: python build.py [--force] [--debug] [--dev] [--stamps]
 
---dev builds the development library libsae_attn_dev.so (schedule-variant knobs read from the
-environment, SAE_DEV_KNOBS); tools load it through SAE_ATTN_LIB.  --stamps builds
-libsae_attn_stamp.so (the dev knobs plus in-kernel s_memtime stamps, tools/stamps.py).  The release library
-libsae_attn.so never reads the environment on a launch path.
+--dev builds the development library libsae_attn_dev.so (SAE_DEV_KNOBS: dispatch knobs read from the
+environment); tools load it through SAE_ATTN_LIB.  Rule: the dev and the release library contain the
+same set of kernels.  A knob chooses among kernels the release launches somewhere, or sets a
+run-time argument; no knob instantiates a kernel of its own, and no shipped kernel keeps a template
+parameter for a schedule that lost its A/B -- rejected variants are deleted once measured
+(DESIGN_HISTORY.md, profiles/ and the git history keep them).  `nm -C <lib> | grep __device_stub__`
+lists the same kernels for both.  --stamps builds libsae_attn_stamp.so (the dev knobs plus in-kernel
+s_memtime stamps, tools/stamps.py).  The release library libsae_attn.so never reads the environment
+on a launch path.
 """
 import argparse
 import hashlib

@@ -10,24 +10,6 @@
 
 namespace sae {
 
-// dK / dV pass of the two-pass backward (bwd2.h) at one wave per SIMD; PIPE = both query halves'
-// S / dP chains issued back to back (see attn_bwd2_dkdv_kernel)
-template <int DP, bool PIPE>
-hipError_t dkdv_agpr_launch(hipStream_t st, const AttnArgs& a) {
-  constexpr int NW = 4;
-  const long long grid = (long long)((a.Nk + 32 * NW - 1) / (32 * NW)) * a.H * a.B;
-  const size_t lds = 2 * (2 * (size_t)F2<DP>::TILE + 512);
-  hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<DP, NW, 1, false, false, PIPE>), dim3((unsigned)grid), dim3(64 * NW), lds,
-                     st, a);
-  return hipGetLastError();
-}
-
-hipError_t bwd2_dkdv_agpr(hipStream_t st, const AttnArgs& a, int dp, bool pipe) {
-  if (dp == 32) return pipe ? dkdv_agpr_launch<32, true>(st, a) : dkdv_agpr_launch<32, false>(st, a);
-  if (dp == 64) return pipe ? dkdv_agpr_launch<64, true>(st, a) : dkdv_agpr_launch<64, false>(st, a);
-  return hipErrorInvalidValue;
-}
-
 // both passes of the two-pass backward (bwd2.h) with the accumulators in AGPRs: dQ pass at MQ waves
 // per SIMD, dK / dV pass at MK (the head_dim 128 instances: BoTNet)
 template <int DP, int MQ, int MK, bool REL>
@@ -55,9 +37,10 @@ hipError_t bwd2_agpr_launch(hipStream_t st, const AttnArgs& a) {
   return hipGetLastError();
 }
 
-hipError_t bwd2_agpr128(hipStream_t st, const AttnArgs& a, bool rel, int variant) {
-  if (variant == 0) return rel ? bwd2_agpr_launch<128, 1, 1, true>(st, a) : bwd2_agpr_launch<128, 1, 1, false>(st, a);
-  return rel ? bwd2_agpr_launch<128, 2, 1, true>(st, a) : bwd2_agpr_launch<128, 2, 1, false>(st, a);
+// head_dim 128: the dK / dV pass at one wave per SIMD; the dQ pass at two, or at one with relative
+// logits (whose state spills at two waves per SIMD; capi.hip attn_bwd_impl)
+hipError_t bwd2_agpr128(hipStream_t st, const AttnArgs& a, bool rel) {
+  return rel ? bwd2_agpr_launch<128, 1, 1, true>(st, a) : bwd2_agpr_launch<128, 2, 1, false>(st, a);
 }
 
 }  // namespace sae

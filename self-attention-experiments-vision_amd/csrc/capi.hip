@@ -10,7 +10,6 @@
 #include <string>
 #include <algorithm>
 #include <type_traits>
-#include <mutex>
 
 #include "../../include/sae_attn.h"
 #include "attn_kernels.h"
@@ -171,14 +170,14 @@ template <typename T, int DP, bool VEC, bool REL> struct FwdL {
 
 // lean bf16 forward (fwd2.h): NW waves x 32 query rows per workgroup
 template <int DP, int NW, int MINW, bool LSUM, bool ROT = false, int NSU = DP / 16, bool REL = false,
-          bool FIX = false, bool PSC = false>
+          bool FIX = false>
 int fwd2_run(hipStream_t st, const AttnArgs& a) {
   const int nqb = (a.Nq + 32 * NW - 1) / (32 * NW);
   const long long grid = (long long)nqb * a.H * a.B;
   if (grid > 0x7fffffffLL) return fail(SAE_EUNSUPPORTED, "grid too large");
   const size_t lds = 4 * (size_t)F2<DP>::TILE + (REL ? 2 * kRelImg : 0);
-  if (int rc = lds_attr((const void*)attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX, PSC>, lds)) return rc;
-  hipLaunchKernelGGL((attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX, PSC>), dim3((unsigned)grid),
+  if (int rc = lds_attr((const void*)attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX>, lds)) return rc;
+  hipLaunchKernelGGL((attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX>), dim3((unsigned)grid),
                      dim3(64 * NW), lds, st, a);
   return check_launch("attn_fwd2");
 }
@@ -211,9 +210,12 @@ template <bool BWD> int cls_run(hipStream_t st, const AttnArgs& a) {
   return check_launch("attn_cls_fwd");
 }
 
-// Development A/B knobs (schedule variants picked by environment variable) exist only in the
-// debug build (build.py --dev defines SAE_DEV_KNOBS); the release library takes the fixed
-// dispatch below and never reads the environment on a launch path.
+// Development A/B knobs, read from the environment only in the dev build (build.py --dev defines
+// SAE_DEV_KNOBS); the release library takes the fixed dispatch and never reads the environment on
+// a launch path.  Rule: both libraries hold the same set of kernels.  A knob chooses among kernels
+// the release launches somewhere, or sets a run-time argument; it never instantiates a kernel of
+// its own.  A schedule that lost its A/B is deleted (DESIGN_HISTORY.md, profiles/ and the git
+// history keep the measurement), not parked behind a knob.
 #ifdef SAE_DEV_KNOBS
 int dev_knob(const char* name) {
   const char* e = getenv(name);
@@ -224,43 +226,22 @@ int dev_knob(const char* name) {
 constexpr int dev_knob(const char*) { return 0; }
 #endif
 
-template <int DP, bool ROT = false> int fwd2_dispatch(hipStream_t st, const AttnArgs& a, int var) {
-#ifdef SAE_DEV_KNOBS
-  if (!ROT) switch (var) {
-    case 2: return fwd2_run<DP, 8, 2, true>(st, a);
-    case 4: return fwd2_run<DP, 4, 2, true>(st, a);
-    case 5: return fwd2_run<DP, 4, 3, true>(st, a);
-    case 6: return fwd2_run<DP, 4, 3, false>(st, a);
-    case 7: return fwd2_run<DP, 4, 3, true, false, DP / 16, false, true>(st, a);
-    case 8: return fwd2_run<DP, 4, 2, true, false, DP / 16, false, true>(st, a);
-    case 9: return fwd2_run<DP, 4, 3, false, false, DP / 16, false, true>(st, a);
-    default: break;
-  }
-  if constexpr (DP <= 64) {
-    if (!ROT && var == 40) return fwd2_run<DP, 4, 3, false, false, DP / 16, false, true, true>(st, a);   // prescaled q
-    if (!ROT && var == 41) return fwd2_run<DP, 4, 3, true, false, DP / 16, false, true, true>(st, a);    // + MFMA row sum
-    if (!ROT && var == 42) return fwd2_run<DP, 4, 2, false, false, DP / 16, false, true, true>(st, a);
-  }
-#endif
-  // D <= 64 without rotary: three waves per SIMD, row sum on the VALU, running max fixed by the
-  // first tile (FIX, with the tracking sweep as the in-kernel fallback): 23.2 vs 24.6 us at
-  // DeiT-S, 95.4 vs 96.5 us at ViT-B@384 (profiles/r03b_fwdvar.txt, bitwise-equal outputs)
-  // (the rotary instances take the same variant: the fused-rotary forward stays bit-equal to the
-  // standalone rotary pass + this forward, tests/test_gpu_rotary.py)
+// The lean forward's variant per padded head dim:
+//   DP <= 64: three waves per SIMD, row sum on the VALU, running max fixed by the first tile (FIX,
+//             with the tracking sweep as the in-kernel fallback): 23.2 vs 24.6 us at DeiT-S, 95.4 vs
+//             96.5 us at ViT-B@384 (profiles/r03b_fwdvar.txt, bitwise-equal outputs).  head_dim <= 48
+//             (CaiT) in 64-wide tiles without rotary: QK^T skips the all-zero fourth k-step (NSU 3).
+//             The rotary instances take the same variant: the fused-rotary forward stays bit-equal
+//             to the standalone rotary pass + this forward (tests/test_gpu_rotary.py).
+//   DP 128:   two waves per SIMD, row sum on the MFMA (the VALU row sum is 2x slower there,
+//             profiles/r01_attn_fwd_f0_vs_f6_interleaved_v13.txt).
+template <int DP, bool ROT = false> int fwd2_dispatch(hipStream_t st, const AttnArgs& a) {
   if constexpr (DP <= 64) {
     if (!ROT && DP == 64 && a.D <= 48) return fwd2_run<DP, 4, 3, false, false, 3, false, true>(st, a);
     return fwd2_run<DP, 4, 3, false, ROT, DP / 16, false, true>(st, a);
+  } else {
+    return fwd2_run<DP, 4, 2, true, ROT>(st, a);
   }
-  // long key ranges at D <= 64: three waves per SIMD, row sum on the VALU is 2.5 % faster at
-  // N = 577 and equal at N = 197 (profiles/r01_attn_fwd_f0_vs_f6_interleaved_v13.txt); at
-  // D = 128 it is 2x slower
-  if constexpr (DP <= 64)
-    if (a.Nk >= 512) return fwd2_run<DP, 4, 3, false, ROT>(st, a);
-  (void)var;
-  // head_dim 48 (CaiT) in 64-wide tiles: QK^T skips the all-zero fourth k-step
-  if constexpr (DP == 64 && !ROT)
-    if (a.D <= 48) return fwd2_run<DP, 4, 2, true, false, 3>(st, a);
-  return fwd2_run<DP, 4, 2, true, ROT>(st, a);
 }
 
 // lean bf16 backward (bwd2.h): dQ pass (publishes delta) then dK/dV pass
@@ -290,38 +271,23 @@ template <int DP, bool ROT = false> int bwd2_run_default(hipStream_t st, const A
 
 }  // namespace
 namespace sae {
-hipError_t bwd2_dkdv_agpr(hipStream_t st, const AttnArgs& a, int dp, bool pipe);   // bwd_agpr.hip
-hipError_t bwd2_agpr128(hipStream_t st, const AttnArgs& a, bool rel, int variant);  // bwd_agpr.hip
+hipError_t bwd2_agpr128(hipStream_t st, const AttnArgs& a, bool rel);  // bwd_agpr.hip
 }
 namespace {
-
-// two-pass backward with the dK / dV pass from bwd_agpr.hip (one wave per SIMD, AGPR accumulators)
-template <int DP> int bwd2_run_agpr(hipStream_t st, const AttnArgs& a, bool pipe) {
-  {
-    const long long grid = (long long)((a.Nq + 127) / 128) * a.H * a.B;
-    if (grid > 0x7fffffffLL) return fail(SAE_EUNSUPPORTED, "grid too large");
-    const size_t lds = 4 * (size_t)F2<DP>::TILE;
-    hipLaunchKernelGGL((attn_bwd2_dq_kernel<DP, 4, 2>), dim3((unsigned)grid), dim3(256), lds, st, a);
-    if (int rc = check_launch("attn_bwd2_dq")) return rc;
-  }
-  const hipError_t e = bwd2_dkdv_agpr(st, a, DP, pipe);
-  if (e != hipSuccess) return fail(SAE_EHIP, "attn_bwd2_dkdv (agpr): %s", hipGetErrorString(e));
-  return ok();
-}
 
 // single-pass bf16 backward (bwd3.h): one workgroup per (batch, head) holding all Nk <= 256 keys
 // (8 waves x 32 keys, two waves per SIMD); longer key ranges take the two-pass bwd2
 constexpr int kB3Keys = 256;
 
-template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16, bool STAG = false, bool PRIO = false>
+template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16>
 int bwd3_run(hipStream_t st, const AttnArgs& a) {
   using C = B3<DP, NW, KPW>;
   static_assert(C::BK == kB3Keys, "bwd3 dispatch assumes 256-key blocks");
   const long long grid = (long long)a.H * a.B;
   if (a.Nk > C::BK) return fail(SAE_EINVAL, "bwd3: %d keys > %d", a.Nk, C::BK);
   if (grid > 0x7fffffffLL) return fail(SAE_EUNSUPPORTED, "grid too large");
-  if (int rc = lds_attr((const void*)attn_bwd3_kernel<DP, NW, KPW, ROT, NSU, STAG, PRIO>, C::LDS)) return rc;
-  hipLaunchKernelGGL((attn_bwd3_kernel<DP, NW, KPW, ROT, NSU, STAG, PRIO>), dim3((unsigned)grid), dim3(64 * NW),
+  if (int rc = lds_attr((const void*)attn_bwd3_kernel<DP, NW, KPW, ROT, NSU>, C::LDS)) return rc;
+  hipLaunchKernelGGL((attn_bwd3_kernel<DP, NW, KPW, ROT, NSU>), dim3((unsigned)grid), dim3(64 * NW),
                      C::LDS, st, a);
   return check_launch("attn_bwd3");
 }
@@ -552,36 +518,23 @@ int th_bwd(void* stream, const sae_attn_desc* d, const void* q, const void* k, c
 }
 
 // ==================================================================================== C ABI
-// one gemm_dw launch (with or without the bias column sums), NG wave groups per workgroup
-template <class XL, class YL, int NG>
-static int dw_launch(const DwArgs& a, bool bias, long long grid, size_t lds, hipStream_t st) {
-  const void* fn = bias ? (const void*)gemm_dw_kernel<true, XL, YL, NG> : (const void*)gemm_dw_kernel<false, XL, YL, NG>;
-  if (int rc = lds_attr(fn, lds)) return rc;
-  if (bias)
-    hipLaunchKernelGGL((gemm_dw_kernel<true, XL, YL, NG>), dim3((unsigned)grid), dim3(256 * NG), lds, st, a);
-  else
-    hipLaunchKernelGGL((gemm_dw_kernel<false, XL, YL, NG>), dim3((unsigned)grid), dim3(256 * NG), lds, st, a);
-  return 0;
-}
-
-// the LDS-DMA form of the plain weight-gradient kernel (gemm_dw8.h)
-template <int NG, int NS = kDw8NS, int STAG = 0>
+// one gemm_dw8 launch (gemm_dw8.h; with or without the bias column sums), NG wave groups per workgroup
+template <int NG>
 static int dw8_launch(const DwArgs& a, bool bias, long long grid, hipStream_t st) {
-  constexpr int lds = dw8_lds_bytes<NG, NS>();
-  const void* fn = bias ? (const void*)gemm_dw8_kernel<true, NG, NS, STAG> : (const void*)gemm_dw8_kernel<false, NG, NS, STAG>;
+  constexpr int lds = dw8_lds_bytes<NG>();
+  const void* fn = bias ? (const void*)gemm_dw8_kernel<true, NG> : (const void*)gemm_dw8_kernel<false, NG>;
   if (int rc = lds_attr(fn, lds)) return rc;
   if (bias)
-    hipLaunchKernelGGL((gemm_dw8_kernel<true, NG, NS, STAG>), dim3((unsigned)grid), dim3(256 * NG), lds, st, a);
+    hipLaunchKernelGGL((gemm_dw8_kernel<true, NG>), dim3((unsigned)grid), dim3(256 * NG), lds, st, a);
   else
-    hipLaunchKernelGGL((gemm_dw8_kernel<false, NG, NS, STAG>), dim3((unsigned)grid), dim3(256 * NG), lds, st, a);
+    hipLaunchKernelGGL((gemm_dw8_kernel<false, NG>), dim3((unsigned)grid), dim3(256 * NG), lds, st, a);
   return 0;
 }
 
 // one sae_gemm_nt launch: TM x 128 tiles, two LDS stage buffers of BK-deep A and B images
 template <int EPI, class AL>
 static int nt_launch(const NtArgs& g, long long grid, hipStream_t st) {
-  size_t lds = 2 * (NtRows<AL>::value + kNtT) * NtDepth<AL>::value * 2;
-  if constexpr (NtIsDma<AL>::value) lds = (size_t)AL::kNB * 2 * kNtT * 32 * 2;
+  const size_t lds = 2 * (NtRows<AL>::value + kNtT) * NtDepth<AL>::value * 2;
   if (int rc = lds_attr((const void*)gemm_nt_kernel<EPI, AL>, lds)) return rc;
   hipLaunchKernelGGL((gemm_nt_kernel<EPI, AL>), dim3((unsigned)grid), dim3(256), lds, st, g);
   return 0;
@@ -612,41 +565,10 @@ static int g8_pick_bm(int M, int N, int BN) {
   return cost(224) < cost(256) ? 224 : 256;
 }
 
-// Work-stealing counters of the persistent gemm8 launches (gemm8.h, DYN; dev builds): 8 group tickets
-// and a done word per slot, each on a 128-byte line of its own; a slot belongs to one stream (launches on one
-// stream are ordered, so a slot is never used by two running launches; the last workgroup of a
-// launch resets it).  A graph captured on a stream keeps that stream's slot in its kernel nodes.
-#ifdef SAE_DEV_KNOBS
-constexpr int kG8Slots = 64, kG8SlotWords = 288;   // 8 group tickets + done, 128 bytes apart
-__device__ unsigned g_g8_ctr[kG8Slots * kG8SlotWords];
-
-static unsigned* g8_slot(hipStream_t st) {
-  static std::mutex mu;
-  static hipStream_t owner[64][kG8Slots];
-  static int used[64] = {0};
-  static unsigned* base[64] = {nullptr};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!base[dev]) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_g8_ctr)) != hipSuccess) return nullptr;
-    base[dev] = reinterpret_cast<unsigned*>(p);
-  }
-  for (int i = 0; i < used[dev]; ++i)
-    if (owner[dev][i] == st) return base[dev] + kG8SlotWords * i;
-  if (used[dev] == kG8Slots) return nullptr;   // more streams than slots: the static walk
-  owner[dev][used[dev]] = st;
-  return base[dev] + kG8SlotWords * used[dev]++;
-}
-#endif
-
-// one persistent gemm8 launch (BM x BN tiles, one 8-wave workgroup per CU).  The work-stealing walk
-// (DYN, dev builds: SAE_G8_DYN=1) measured 3 % slower on the DeiT-S step and no better under the
-// one-GPU RCCL contention emulation (profiles/r06c_g8_dyn_ab.txt), so the release walk is static.
+// one persistent gemm8 launch (BM x BN tiles, one 8-wave workgroup per CU)
 template <int EPI, int BN, int BK, int NS, int BM, int WGM = 2, bool XW = false>
 static int g8_launch_bm(const NtArgs& g0, hipStream_t st) {
-  constexpr int lds = g8_lds_bytes<BN, BK, NS, WGM>() + kG8TickBytes;
+  constexpr int lds = g8_lds_bytes<BN, BK, NS, WGM>();
   const long long tiles = (long long)((g0.M + BM - 1) / BM) * ((g0.N + BN - 1) / BN);
   const long long grid = std::min<long long>(tiles, device_cus());
   NtArgs g = g0;
@@ -656,37 +578,17 @@ static int g8_launch_bm(const NtArgs& g0, hipStream_t st) {
   // The multiply's aux (gelu'(h)) tile loaded non-temporal: level in isolation, DeiT-S step
   // 8.01 -> 7.85 ms (profiles/r06z4_g8_aux_nt_ab.txt)
   g.nts = ((EPI != kEpiDGelu || WGM == 4) && !dev_knob("SAE_G8_NO_NTS") ? 1 : 0) | (!dev_knob("SAE_G8_NO_AUX_NT") ? 2 : 0);
-#ifdef SAE_DEV_KNOBS
-  g.ctr = (NS == 2 && tiles > grid && grid >= 8 && dev_knob("SAE_G8_DYN")) ? g8_slot(st) : nullptr;
-  if (g.ctr) {
-    if constexpr (NS == 2) {
-      if (int rc = lds_attr((const void*)gemm8_nt_kernel<EPI, BN, BK, NS, 0, BM, true>, lds)) return rc;
-      hipLaunchKernelGGL((gemm8_nt_kernel<EPI, BN, BK, NS, 0, BM, true>), dim3((unsigned)grid), dim3(512), lds, st, g);
-      return 0;
-    }
-  }
-#endif
-  if (int rc = lds_attr((const void*)gemm8_nt_kernel<EPI, BN, BK, NS, 0, BM, false, WGM, XW>, lds)) return rc;
-  hipLaunchKernelGGL((gemm8_nt_kernel<EPI, BN, BK, NS, 0, BM, false, WGM, XW>), dim3((unsigned)grid), dim3(512), lds, st, g);
+  if (int rc = lds_attr((const void*)gemm8_nt_kernel<EPI, BN, BK, NS, BM, WGM, XW>, lds)) return rc;
+  hipLaunchKernelGGL((gemm8_nt_kernel<EPI, BN, BK, NS, BM, WGM, XW>), dim3((unsigned)grid), dim3(512), lds, st, g);
   return 0;
 }
 template <int EPI, int BN, int BK, int NS>
 static int g8_launch(const NtArgs& g, hipStream_t st) {
-#ifdef SAE_DEV_KNOBS
-  if constexpr (BK == 64 && NS == 2) {   // dev A/B: 32-deep stages, 4-deep ring (three stages in flight)
-    if (dev_knob("SAE_G8_DEPTH") == 1)
-      return g8_pick_bm(g.M, g.N, BN) == 224 ? g8_launch_bm<EPI, BN, 32, 4, 224>(g, st)
-                                             : g8_launch_bm<EPI, BN, 32, 4, 256>(g, st);
-  }
-#endif
   // plain 192-wide tiles: whole-row epilogue stores through the shared row image (XW): QKV forward
   // 32.9 -> 31.4 us, DeiT-S step -0.13 % (profiles/r06xw_g8_xw_ab.txt)
-  if constexpr (EPI == kEpiNone && BN == 192)
-    if (!dev_knob("SAE_G8_NO_XW"))
-      return g8_pick_bm(g.M, g.N, BN) == 224 ? g8_launch_bm<EPI, BN, BK, NS, 224, 2, true>(g, st)
-                                             : g8_launch_bm<EPI, BN, BK, NS, 256, 2, true>(g, st);
-  return g8_pick_bm(g.M, g.N, BN) == 224 ? g8_launch_bm<EPI, BN, BK, NS, 224>(g, st)
-                                         : g8_launch_bm<EPI, BN, BK, NS, 256>(g, st);
+  constexpr bool XW = EPI == kEpiNone && BN == 192;
+  return g8_pick_bm(g.M, g.N, BN) == 224 ? g8_launch_bm<EPI, BN, BK, NS, 224, 2, XW>(g, st)
+                                         : g8_launch_bm<EPI, BN, BK, NS, 256, 2, XW>(g, st);
 }
 
 // GELU forward at K < 768 (the epilogue's VALU work, which scales with the outputs, outweighs the
@@ -831,15 +733,15 @@ static int attn_fwd_impl(void* stream, const sae_attn_desc* d, const void* q, co
       return fail(SAE_EUNSUPPORTED, "rotary: fused only on the bf16 path with head_dim <= 64 (16-byte aligned "
                   "strides, no flags)");
     a.rope = *rope;
-    if (dp == 32) return fwd2_dispatch<32, true>((hipStream_t)stream, a, 0);
-    return fwd2_dispatch<64, true>((hipStream_t)stream, a, 0);
+    if (dp == 32) return fwd2_dispatch<32, true>((hipStream_t)stream, a);
+    return fwd2_dispatch<64, true>((hipStream_t)stream, a);
   }
   if (var != 1 && vec && cls_ok(d)) return cls_run<false>((hipStream_t)stream, a);
   if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && !rel) {
     const int dp = pick_dp(d->head_dim);
-    if (dp == 32) return fwd2_dispatch<32>((hipStream_t)stream, a, var);
-    if (dp == 64) return fwd2_dispatch<64>((hipStream_t)stream, a, var);
-    if (dp == 128) return fwd2_dispatch<128>((hipStream_t)stream, a, var);
+    if (dp == 32) return fwd2_dispatch<32>((hipStream_t)stream, a);
+    if (dp == 64) return fwd2_dispatch<64>((hipStream_t)stream, a);
+    if (dp == 128) return fwd2_dispatch<128>((hipStream_t)stream, a);
   }
   if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && rel && rel_lean(a)) {   // BoTNet
     const int dp = pick_dp(d->head_dim);
@@ -925,50 +827,28 @@ static int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, co
     a.rope = *rope;
     hipStream_t st = (hipStream_t)stream;
     if (a.Nk <= kB3Keys)
-      return dp == 32 ? bwd3_run<32, 8, 1, true, 2, true>(st, a) : bwd3_run<64, 8, 1, true, 4, true>(st, a);
+      return dp == 32 ? bwd3_run<32, 8, 1, true, 2>(st, a) : bwd3_run<64, 8, 1, true, 4>(st, a);
     return dp == 32 ? bwd2_run_default<32, true>(st, a) : bwd2_run_default<64, true>(st, a);
   }
   if (var != 1 && vec && cls_ok(d)) return cls_run<true>((hipStream_t)stream, a);
   if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && !rel) {
     const int dp = pick_dp(d->head_dim);
     hipStream_t st = (hipStream_t)stream;
-    if (a.Nk <= kB3Keys && var != 2 && var < 10 && dp <= 64) {
-#ifdef SAE_DEV_KNOBS
-      if (var == 3) {   // four waves x two 32-key sub-blocks (one wave per SIMD): measured slower
-        if (dp == 32) return bwd3_run<32, 4, 2>(st, a);
-        if (dp == 64) return bwd3_run<64, 4, 2>(st, a);
-      }
-      if (var >= 5 && var <= 7 && dp == 64) {   // no stagger / stagger + priority / priority only
-        const bool d48 = d->head_dim <= 48;
-        if (var == 5) return d48 ? bwd3_run<64, 8, 1, false, 3>(st, a) : bwd3_run<64, 8, 1, false, 4>(st, a);
-        if (var == 6) return d48 ? bwd3_run<64, 8, 1, false, 3, true, true>(st, a) : bwd3_run<64, 8, 1, false, 4, true, true>(st, a);
-        return d48 ? bwd3_run<64, 8, 1, false, 3, false, true>(st, a) : bwd3_run<64, 8, 1, false, 4, false, true>(st, a);
-      }
-#endif
-      // waves 4-7 staggered (the previous tile's dQ first): DeiT-S 53.6 -> 53.2 us, CaiT-S24
-      // 130.7 -> 128.3 us (profiles/r06g_bwd3_stagger_ab.txt; same sums, bit-identical results)
-      if (dp == 32) return bwd3_run<32, 8, 1, false, 2, true>(st, a);
-      if (dp == 64 && d->head_dim <= 48) return bwd3_run<64, 8, 1, false, 3, true>(st, a);   // CaiT head_dim 48
-      if (dp == 64) return bwd3_run<64, 8, 1, false, 4, true>(st, a);
+    if (a.Nk <= kB3Keys && var != 2 && dp <= 64) {
+      // (waves 4-7 staggered, the previous tile's dQ first: DeiT-S 53.6 -> 53.2 us, CaiT-S24
+      // 130.7 -> 128.3 us, profiles/r06g_bwd3_stagger_ab.txt; same sums, bit-identical results)
+      if (dp == 32) return bwd3_run<32, 8, 1, false, 2>(st, a);
+      if (dp == 64 && d->head_dim <= 48) return bwd3_run<64, 8, 1, false, 3>(st, a);   // CaiT head_dim 48
+      if (dp == 64) return bwd3_run<64, 8, 1, false, 4>(st, a);
     }
-#ifdef SAE_DEV_KNOBS
-    if (dp == 64 && (var == 10 || var == 11)) return bwd2_run_agpr<64>(st, a, var == 11);
-#endif
     if (dp == 32) return bwd2_run_default<32>(st, a);
     if (dp == 64) return bwd2_run_default<64>(st, a);
-#ifdef SAE_DEV_KNOBS
-    if (var == 30) {
-      const hipError_t e = bwd2_agpr128(st, a, false, 0);
-      return e == hipSuccess ? ok() : fail(SAE_EHIP, "bwd2 agpr: %s", hipGetErrorString(e));
-    }
-    if (var == 32) return bwd2_run<128, 4, 1, 4, 1>(st, a);
-#endif
     // head_dim 128 (BoTNet): the dK / dV pass at one wave per SIMD (the dK / dV accumulators of 32
     // keys x 128 columns plus the K / V fragments need more than half the register file), built in
     // the AGPR translation unit (bwd_agpr.hip: accumulators in AGPRs, no spills; bot14 bwd
     // 222 -> 216 us, bot7 49 -> 47 us same box, profiles/r03f_bot_agpr_ab.txt)
     {
-      const hipError_t e = bwd2_agpr128(st, a, false, 1);
+      const hipError_t e = bwd2_agpr128(st, a, false);
       return e == hipSuccess ? ok() : fail(SAE_EHIP, "attn_bwd2 (head_dim 128): %s", hipGetErrorString(e));
     }
   }
@@ -981,7 +861,7 @@ static int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, co
     // unit (the dQ pass's relative-logit state spills 75 VGPRs at two waves per SIMD): bot14+rel
     // bwd 315 -> 298 us; the 7 x 7 grid keeps the two-wave dQ pass (59 vs 67 us)
     if (a.Nk >= 128) {
-      const hipError_t e = bwd2_agpr128(st, a, true, 0);
+      const hipError_t e = bwd2_agpr128(st, a, true);
       return e == hipSuccess ? ok() : fail(SAE_EHIP, "attn_bwd2 (relpos, head_dim 128): %s", hipGetErrorString(e));
     }
     return bwd2_run<128, 4, 2, 4, 1, false, true>(st, a);
@@ -1231,18 +1111,13 @@ static int gemm_dw_impl(void* stream, int32_t M, int32_t I, int32_t J, const voi
   a.M = M;
   a.I = I;
   a.J = J;
-  // wave groups per workgroup (gemm_dw.h): two for small outputs (<= 64 tiles of 128 x 128: every
+  // wave groups per workgroup (gemm_dw8.h): two for small outputs (<= 64 tiles of 128 x 128: every
   // DeiT-S / CaiT projection), where half the splits still fill the chip and halve the fp32
   // partial traffic (output projection dW + reduce 34.8 -> 30.6 us); one for the larger ViT-B
   // outputs, where halving the splits would leave CUs idle (FF 139 -> 205 us)
   const int tiles = ((I + kDwT - 1) / kDwT) * ((J + kDwT - 1) / kDwT);
-  int NG = tiles <= 64 ? 2 : 1;
-  int dw8v = 0;   // dev A/B: 1 = one 4-wave group with an 8-deep ring (one workgroup per CU)
-#ifdef SAE_DEV_KNOBS
-  dw8v = dev_knob("SAE_DW8_VARIANT");
-  if (dw8v == 1) NG = 1;
-#endif
-  dw_plan(M, I, J, &a.S, &a.chunk, dw8v == 1 ? 256 : 512 / NG);
+  const int NG = tiles <= 64 ? 2 : 1;
+  dw_plan(M, I, J, &a.S, &a.chunk, 512 / NG);
   if ((long long)(a.chunk + 4 * NG * kDwK) * std::max(ldx, ldy) * 2 >= (1LL << 31))
     return fail(SAE_EUNSUPPORTED, "gemm_dw: token chunk exceeds 32-bit buffer addressing");
   a.part = reinterpret_cast<float*>(workspace);
@@ -1257,31 +1132,7 @@ static int gemm_dw_impl(void* stream, int32_t M, int32_t I, int32_t J, const voi
   a.jblock = jblock;
   hipStream_t st = (hipStream_t)stream;
   const long long grid = (long long)a.S * ((I + kDwT - 1) / kDwT) * ((J + kDwT - 1) / kDwT);
-  const size_t lds = NG * 4 * kDwK * 256;
-  typedef DwRow<false> XR;
-  typedef DwRow<true> YR;
-  bool dma = true;
-#ifdef SAE_DEV_KNOBS
-  dma = !dev_knob("SAE_DW_OLD");
-#endif
-  if (dma && dw8v == 1) {
-    if (int rc = dw8_launch<1, 8>(a, db != nullptr, grid, st)) return rc;
-#ifdef SAE_DEV_KNOBS
-  } else if (dma && NG == 2 && (dw8v == 2 || dw8v == 3)) {   // wave-group offset A/B: none / a whole stage
-    if (int rc = dw8v == 2 ? dw8_launch<2, kDw8NS, 0>(a, db != nullptr, grid, st)
-                           : dw8_launch<2, kDw8NS, 1>(a, db != nullptr, grid, st))
-      return rc;
-#endif
-  } else if (dma) {
-    // two wave groups half a stage apart (STAG 2): DeiT-S step 8.148 -> 8.056 ms same box
-    // (profiles/r06h_dw8_stagger_ab.txt); a whole stage apart measured level
-    if (int rc = NG == 2 ? dw8_launch<2, kDw8NS, 2>(a, db != nullptr, grid, st) : dw8_launch<1>(a, db != nullptr, grid, st))
-      return rc;
-  } else if (NG == 2) {
-    if (int rc = dw_launch<XR, YR, 2>(a, db != nullptr, grid, lds, st)) return rc;
-  } else {
-    if (int rc = dw_launch<XR, YR, 1>(a, db != nullptr, grid, lds, st)) return rc;
-  }
+  if (int rc = NG == 2 ? dw8_launch<2>(a, db != nullptr, grid, st) : dw8_launch<1>(a, db != nullptr, grid, st)) return rc;
   if (int rc = check_launch("gemm_dw")) return rc;
   const long long n4 = (long long)I * J / 4;
   const unsigned rb = (unsigned)std::min<long long>((n4 + kDwRedCols - 1) / kDwRedCols, 4096);
@@ -1470,8 +1321,7 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
     if (epilogue == SAE_EPI_GELU && g8_gelu_bn128(M, N, K)) {
       // 4 x 2 waves (64 x 64 wave tiles): whole 128-byte output lines per wave row segment --
       // writes 172 -> 155 MB (= algorithmic), 57.1 -> 54.8 us at DeiT-S (profiles/r06w4_g8_wgm4_ab.txt)
-      if (int rc = dev_knob("SAE_G8_WGM2") ? g8_launch_bm<kEpiGelu, 128, 64, 2, 256>(g, st)
-                                           : g8_launch_bm<kEpiGelu, 128, 64, 2, 256, 4>(g, st)) return rc;
+      if (int rc = g8_launch_bm<kEpiGelu, 128, 64, 2, 256, 4>(g, st)) return rc;
       return check_launch("gemm8_nt");
     }
     // the gelu' multiply on the same 256 x 128 tiles and 4 x 2 waves (whole-line stores, now also
@@ -1498,19 +1348,6 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
 #ifdef SAE_DEV_KNOBS
   const int ntv = dev_knob("SAE_NT_VARIANT");
   if (ntv) tall = ntv == 2;
-  if ((ntv == 3 || ntv == 4) && K % kNtK == 0) {   // LDS-DMA staging, 3 / 4 stage buffers (no K tail)
-    int rc;
-    if (ntv == 3)
-      rc = epilogue == SAE_EPI_NONE ? nt_launch<kEpiNone, NtDmaA<3>>(g, grid128, st)
-           : epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, NtDmaA<3>>(g, grid128, st)
-                                      : nt_launch<kEpiDGelu, NtDmaA<3>>(g, grid128, st);
-    else
-      rc = epilogue == SAE_EPI_NONE ? nt_launch<kEpiNone, NtDmaA<4>>(g, grid128, st)
-           : epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, NtDmaA<4>>(g, grid128, st)
-                                      : nt_launch<kEpiDGelu, NtDmaA<4>>(g, grid128, st);
-    if (rc) return rc;
-    return check_launch("gemm_nt");
-  }
 #endif
   const int TM = tall ? 256 : kNtT;
   const long long grid = (long long)((M + TM - 1) / TM) * tn;

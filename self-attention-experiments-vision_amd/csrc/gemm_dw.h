@@ -1,8 +1,10 @@
-// gemm_dw.h -- weight / bias gradients of the projections on the hot path, split over tokens.
+// gemm_dw.h -- what the weight / bias gradient kernels share (DwArgs, the split plan's constants,
+// the transposed fragment read, the split reduction) and the register-staged kernel of the
+// patch-embedding gradient.
 //
 // For every Dense / DenseGeneral of the path (QKV projection `queries|keys|values`,
 // attention.py:29-37; output projection `DenseGeneral_0`, attention.py:60-63; the FF block's
-// `Dense_0/1`, ff.py:8-34) the backward needs
+// `Dense_0/1`, ff.py:8-34; the patch embedding) the backward needs
 //     dW[i][j] = sum_m X[m][i] dY[m][j]      (fp32, the parameter dtype)
 //     db[j]    = sum_m dY[m][j]
 // with m running over every token of the batch (M = B*N = 25,216 for DeiT-S) and a small
@@ -10,13 +12,15 @@
 // (tools/gemm_probe.py); here it is a split-K MFMA kernel:
 //   * a workgroup owns a 128 x 128 output tile and one contiguous chunk of tokens; 4 waves,
 //     each a 64 x 64 quarter (2 x 2 accumulators of v_mfma_f32_32x32x16_bf16);
-//   * X and dY chunks of 64 tokens are staged global -> registers -> LDS as [token][column]
-//     images (XOR-swizzled 256-byte rows), double-buffered in LDS with two register stages in
-//     flight (loads issued two stages ahead of use), and both MFMA operands are read
+//   * both MFMA operands are read from [token][column] LDS images (XOR-swizzled 256-byte rows)
 //     with ds_read_b64_tr_b16 (K = tokens on the transposed axis, same permuted K order on both);
 //   * db rides on the matrix pipe: an all-ones A operand times the dY fragment gives column sums;
-//   * each split writes an fp32 partial tile; a second kernel sums the splits in a fixed order
-//     (deterministic, no atomics) and writes / accumulates the fp32 gradient.
+//   * each split writes an fp32 partial tile; gemm_dw_reduce_kernel sums the splits in a fixed
+//     order (deterministic, no atomics) and writes / accumulates the fp32 gradient.
+// The projections' row-major operands take gemm_dw8_kernel (gemm_dw8.h: LDS-DMA staging).
+// gemm_dw_kernel below serves the patch embedding, whose X operand is gathered from the image
+// (patch.h loaders): chunks of 64 tokens staged global -> registers -> LDS, double-buffered in
+// LDS with two register stages in flight (loads issued two stages ahead of use).
 #pragma once
 #include "common.h"
 
@@ -65,9 +69,9 @@ struct DwStage {
   }
 };
 
-// Operand loaders of the plain kernel: token rows [m0, m1) of the row-major x [M][I] / dy [M][J]
-// through buffer descriptors (rows past m1 read zero), columns col0 .. col0 + 127.  patch.h
-// supplies the patch-gather loaders.
+// Row-major operand loader (the dY of the NHWC patch embedding): token rows [m0, m1) of x [M][I] /
+// dy [M][J] through buffer descriptors (rows past m1 read zero), columns col0 .. col0 + 127.
+// patch.h supplies the patch-gather loaders.
 template <bool Y>
 struct DwRow {
   DwStage<4> s;
@@ -94,12 +98,9 @@ __device__ __forceinline__ bf16x8 dw_colfrag(const char* img, const unsigned* ca
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// NG = 2: two groups of 4 waves per workgroup split the token chunk's stages (group g takes
-// stages g, g + 2, ...; own LDS buffers) and add their accumulators through LDS at the end, group
-// 0 first (fixed order): half the splits, so half the fp32 partial-tile traffic, at the same number
-// of waves in flight (one 8-wave workgroup per CU instead of two 4-wave ones).
-template <bool BIAS, class XL = DwRow<false>, class YL = DwRow<true>, int NG = 1>
-__global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm_dw_kernel(DwArgs a) {
+template <bool BIAS, class XL, class YL>
+__global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
   constexpr int IMG = kDwK * 256;     // 16 KiB per operand image
   const int ti = (a.I + kDwT - 1) / kDwT, tj = (a.J + kDwT - 1) / kDwT;
@@ -110,9 +111,9 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm_dw_kernel(DwAr
   const int tile = bid % (ti * tj), s = bid / (ti * tj);
   const int it = tile % ti, jt = tile / ti;
   const int i0 = it * kDwT, j0 = jt * kDwT;
+  // (the mask changes no value in a 256-thread workgroup, but hipcc allocates registers
+  // differently without it: the HWCN fp32 + bias instance then spills a VGPR)
   const int tid = threadIdx.x & 255, lane = tid & 63, h = lane >> 5;
-  const int grp = NG == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-  char* const smem = smem_all + grp * 4 * IMG;   // this group's two stage buffers
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wi = w & 1, wj = w >> 1;  // this wave's 64 x 64 quarter
   const int m0 = s * a.chunk;
@@ -128,16 +129,14 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm_dw_kernel(DwAr
     xs[r].init(a, tid, m0, m1, i0);
     ys[r].init(a, tid, m0, m1, j0);
   }
-  // this group's stage count (group g's stage q is the chunk's stage NG q + g; past the chunk's
-  // end the rows read zero)
-  const int nst = ((m1 - m0 + kDwK - 1) / kDwK + NG - 1) / NG;
+  const int nst = (m1 - m0 + kDwK - 1) / kDwK;
   // straight-line staging (as gemm_nt.h): stage loads / LDS writes past the end are issued
   // unconditionally (they read zeros: rows past m1 are zero) so the waitcnt pass keeps two
   // register stages in flight instead of draining the queue before every reload
-  xs[0].load(a, grp);
-  ys[0].load(a, grp);
-  xs[1].load(a, NG + grp);
-  ys[1].load(a, NG + grp);
+  xs[0].load(a, 0);
+  ys[0].load(a, 0);
+  xs[1].load(a, 1);
+  ys[1].load(a, 1);
 
   unsigned ca[8];   // [operand x / dy][t = 0, 1][r1, r2] transposed-read addresses
   {
@@ -191,8 +190,8 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm_dw_kernel(DwAr
       const char* imx = smem + bsel * 2 * IMG;
       char* nxt = smem + (bsel ^ 1) * 2 * IMG;
       // register set bsel was written to LDS at the end of the previous stage: refill (stage + 2)
-      xs[bsel].load(a, (st + bsel + 2) * NG + grp);
-      ys[bsel].load(a, (st + bsel + 2) * NG + grp);
+      xs[bsel].load(a, st + bsel + 2);
+      ys[bsel].load(a, st + bsel + 2);
       compute(imx, imx + IMG);
       xs[bsel ^ 1].write(nxt);
       ys[bsel ^ 1].write(nxt + IMG);
@@ -200,37 +199,6 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm_dw_kernel(DwAr
     }
   }
   if (st < nst) compute(smem, smem + IMG);   // odd stage count: the last stage sits in buffer 0
-  if constexpr (NG == 2) {
-    // group 1 hands its accumulators to group 0 through the (now free) stage buffers: per wave
-    // 16 KiB of dW (+ 8 KiB of db), lane-contiguous
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem_all) + w * (4 * 16 * 64);
-    float* redb = reinterpret_cast<float*>(smem_all + 4 * 16384) + w * (2 * 16 * 64);
-    if (grp == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(q * 16 + r) * 64 + lane] = acc[q >> 1][q & 1][r];
-      if (bias) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) redb[(q * 16 + r) * 64 + lane] = accb[q][r];
-      }
-    }
-    __syncthreads();
-    if (grp == 1) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[q >> 1][q & 1][r] += red[(q * 16 + r) * 64 + lane];
-    if (bias) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accb[q][r] += redb[(q * 16 + r) * 64 + lane];
-    }
-  }
   // fp32 partial tile: accumulator row = i (row_of), column = j (lane)
   float* P = a.part + (size_t)s * a.I * a.J;
   const int jc = j0 + 64 * wj + (lane & 31);

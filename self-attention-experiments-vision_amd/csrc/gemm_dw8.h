@@ -25,8 +25,8 @@ constexpr int kDw8K = 32;                  // tokens per stage
 constexpr int kDw8NS = 4;                  // ring depth per wave group
 constexpr int kDw8Img = kDw8K * 256;       // one [32][128] bf16 operand image (8 KiB)
 constexpr int kDw8Stage = 2 * kDw8Img;     // X + dY
-template <int NG, int NS = kDw8NS> constexpr int dw8_lds_bytes() {
-  constexpr int ring = NG * NS * kDw8Stage;
+template <int NG> constexpr int dw8_lds_bytes() {
+  constexpr int ring = NG * kDw8NS * kDw8Stage;
   constexpr int red = NG == 2 ? 4 * 16384 + 4 * 8192 : 0;   // group 1 -> group 0 hand-off
   return ring > red ? ring : red;
 }
@@ -44,13 +44,19 @@ template <int N> __device__ __forceinline__ void dw8_wait(int ahead) {
   }
 }
 
-// STAG (NG = 2; dev A/B): the two wave groups (waves 0-3 / 4-7, SIMD partners) offset by one
-// barrier -- 1: one barrier per stage (a whole stage apart); 2: a second barrier between the two
-// k-steps of a stage (half a stage apart) -- so that partners do not read LDS and issue MFMAs in
-// lockstep.  Each group reads only its own ring, so the offset moves no data hazard.
-template <bool BIAS, int NG, int NS = kDw8NS, int STAG = 0>
-__global__ __launch_bounds__(256 * NG, NG == 1 && NS <= 4 ? 2 : 1) void gemm_dw8_kernel(DwArgs a) {
-  static_assert(STAG == 0 || NG == 2, "stagger: two wave groups");
+// NG = 1: one 4-wave group, two workgroups per CU.  NG = 2: two groups of 4 waves per workgroup
+// split the token chunk's stages (group g takes stages g, g + 2, ...; own ring) and add their
+// accumulators through LDS at the end, group 0 first (fixed order): half the splits, so half the
+// fp32 partial-tile traffic, at the same number of waves in flight.  The two groups (waves 0-3 /
+// 4-7, SIMD partners) run half a stage apart -- group 1 starts one barrier late and a second
+// barrier sits between the two k-steps of a stage -- so that partners do not read LDS and issue
+// MFMAs in lockstep (DeiT-S step 8.148 -> 8.056 ms, profiles/r06h_dw8_stagger_ab.txt).  Each group
+// reads only its own ring, so the offset moves no data hazard.
+template <bool BIAS, int NG>
+__global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm_dw8_kernel(DwArgs a) {
+  static_assert(NG == 1 || NG == 2, "one or two wave groups");
+  constexpr int NS = kDw8NS;
+  constexpr bool STAG = NG == 2;
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
   const int ti = (a.I + kDwT - 1) / kDwT, tj = (a.J + kDwT - 1) / kDwT;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);   // as gemm_dw_kernel: a chunk's tiles on one XCD
@@ -132,7 +138,7 @@ __global__ __launch_bounds__(256 * NG, NG == 1 && NS <= 4 ? 2 : 1) void gemm_dw8
     const char* imy = imx + kDw8Img;
 #pragma unroll
     for (int k = 0; k < kDw8K / 16; ++k) {
-      if (STAG == 2 && k == 1) {
+      if (STAG && k == 1) {
         asm volatile("s_barrier" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
       }

@@ -43,8 +43,8 @@ def main():
     ap.add_argument("--rope", action="store_true", help="fused rotary (base 10000) on q / k (--th)")
     ap.add_argument("--rel", action="store_true",
                     help="BoTNet relative logits (square Hs = Ws = sqrt(Nk) grid, N(0, 1/D) bias tables)")
-    ap.add_argument("--fwd-variants", default="", help="comma list of SAE_FWD_VARIANT values to A/B (dev build: SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so)")
-    ap.add_argument("--bwd-variants", default="", help="comma list of SAE_BWD_VARIANT values to A/B")
+    ap.add_argument("--fwd-variants", default="", help="comma list of SAE_FWD_VARIANT values to A/B: 0 = default, 1 = v1 kernels (dev build: SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so)")
+    ap.add_argument("--bwd-variants", default="", help="comma list of SAE_BWD_VARIANT values to A/B: 0 = default, 1 = v1 kernels, 2 = two-pass bwd2 at Nk <= 256")
     ap.add_argument("--knob", default="", help="NAME=v1,v2,...: any dev-library knob to A/B (dev build)")
     args = ap.parse_args()
     import torch

@@ -1,6 +1,7 @@
 #!/bin/bash
-# A/B of attention schedule variants on the development library (build.py --dev) + PMC passes.
+# A/B of the attention dispatch knobs of the development library (build.py --dev) + PMC passes.
 # usage (on the GPU box): tools/gpu_ab.sh <tag> <shapes> <bwd-variants> [fwd-variants]
+# (SAE_BWD_VARIANT: 0 default, 1 v1 kernels, 2 two-pass bwd2 at Nk <= 256; SAE_FWD_VARIANT: 0, 1 v1 kernels)
 set -e
 tag=$1; shapes=$2; bv=$3; fv=${4:-0}
 export TMPDIR=/tmp

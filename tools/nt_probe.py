@@ -3,9 +3,8 @@
 
     SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so python tools/nt_probe.py
 
-Needs the dev library (SAE_NT_VARIANT: 1 = 128-token tiles, 2 = 256-token tiles, 3 / 4 = LDS-DMA
-staging with 3 / 4 stage buffers, 0 = the release policy; NT_VARIANTS picks them, the first is the
-bit-equality reference; NT_PROBE_SHAPES filters shapes).  Per shape: y = x W (fwd, bt = W^T), dX = dY W^T, and for the FF shapes the GELU
+Needs the dev library (SAE_NT_VARIANT: 1 = 128-token tiles, 2 = 256-token tiles, 0 = the release
+policy; NT_VARIANTS picks them, the first is the bit-equality reference; NT_PROBE_SHAPES filters shapes).  Per shape: y = x W (fwd, bt = W^T), dX = dY W^T, and for the FF shapes the GELU
 and GELU' epilogues; each variant's output is checked bit-equal to the 128-token tile's.
 """
 import os

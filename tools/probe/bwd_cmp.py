@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Backward variants of the dev library against float64 autograd (max |g - ref| / max |ref| for dq,
-dk, dv), key ranges > 256 (the two-pass / bwd5 path).  SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so."""
+"""Backward dispatch of the dev library (argv[1]: comma list of SAE_BWD_VARIANT values, 0 = default,
+1 = v1 kernels, 2 = two-pass bwd2 at Nk <= 256) against float64 autograd (max |g - ref| / max |ref|
+for dq, dk, dv), key ranges > 256 (the two-pass path).  SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so."""
 import math
 import os
 import sys

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Forward variants of the dev library against a float64 reference (max |o - ref| / max |ref|, lse
-max abs error), several shapes incl. ragged ones.  SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so."""
+"""Forward dispatch of the dev library (argv[1]: comma list of SAE_FWD_VARIANT values, 0 = default,
+1 = v1 kernels) against a float64 reference (max |o - ref| / max |ref|, lse max abs error), several
+shapes incl. ragged ones.  SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so."""
 import math
 import os
 import sys

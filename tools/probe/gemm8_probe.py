@@ -2,6 +2,8 @@
 """gemm8.h variants (tools/probe/libgemm8_probe.so) against the release sae_gemm_nt and the library
 GEMM at the projection / FF shapes: correctness vs an fp32 product, TF/s (events around 20 launches).
 
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -I include tools/probe/gemm8_probe.hip \
+        -o tools/probe/libgemm8_probe.so
     python tools/probe/gemm8_probe.py [variants=0,1,2,...] [shapes=s_qkv,...]
 """
 import ctypes
