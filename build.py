@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Build libsae_attn.so in-tree for gfx950 (hipcc cross-compiles; no GPU needed).
 
-Usage: python build.py [--force] [--debug] [--dev] [--stamps]
+Usage: python build.py [--force] [--debug] [--dev] [--stamps] [--list-units]
+
+The library is one translation unit per kernel family (UNITS below), compiled in parallel and
+cached per unit.  UNITS is the only list of them: --list-units prints it (`source<TAB>extra flags`)
+for the shell tools, object_files() gives the objects of the last build to the tests.
 
 --dev builds the development library libsae_attn_dev.so (SAE_DEV_KNOBS: dispatch knobs read from the
 environment); tools load it through SAE_ATTN_LIB.  Rule: the dev and the release library contain the
@@ -58,18 +62,18 @@ def unit_deps(path, seen=None):
     return seen
 
 
-# translation units: (source, extra flags).  capi.hip keeps every MFMA accumulator in VGPRs
-# (-amdgpu-mfma-vgpr-form: the exp / rescale VALU reads them directly); bwd_agpr.hip holds the
-# one-wave-per-SIMD kernels, whose dK / dV accumulators go to the AGPR half of the register file.
-UNITS = [("capi.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("bwd_agpr.hip", [])]
+# translation units: (source, extra flags).  Every unit keeps its MFMA accumulators in VGPRs
+# (-amdgpu-mfma-vgpr-form: the exp / rescale VALU reads them directly) except bwd_agpr.hip, which
+# holds the one-wave-per-SIMD kernels whose dK / dV accumulators go to the AGPR half of the
+# register file.  A kernel instance is named by one unit only (tests/test_build_units_cpu.py).
+VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+UNITS = [("attn.hip", VGPR_FORM), ("th.hip", VGPR_FORM), ("gemm.hip", VGPR_FORM), ("misc.hip", VGPR_FORM),
+         ("bwd_agpr.hip", [])]
 
 
-def build(force=False, debug=False, verbose=True, dev=False, stamps=False):
+def _plan(debug=False, dev=False, stamps=False):
+    """(library, common compile command, object directory) of one library flavour."""
     out = OUT_STAMP if stamps else (OUT_DEV if dev else OUT)
-    if not force and up_to_date(out):
-        if verbose:
-            print(f"[build] {out} is up to date")
-        return out
     common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
               "-fno-honor-nans", "-fno-slp-vectorize", "-I", os.path.join(ROOT, "include")]
     if debug:
@@ -81,15 +85,28 @@ def build(force=False, debug=False, verbose=True, dev=False, stamps=False):
     tag = os.path.basename(out).replace(".so", "") + ("_g" if debug else "")
     # objects cached per library flavour and compile command (compiler, arch, flags: a change of
     # any of them is a different directory): a unit is recompiled only when it or a header it
-    # includes changed (capi.hip takes ~2 minutes; the attention units seconds)
+    # includes changed (the slowest unit, attn.hip, takes about 45 s; th.hip 20 s)
     key = hashlib.sha1(repr((common, UNITS)).encode()).hexdigest()[:12]
-    objdir = os.path.join(ROOT, "build", f"{tag}_{ARCH}_{key}")
+    return out, common, os.path.join(ROOT, "build", f"{tag}_{ARCH}_{key}")
+
+
+def object_files(**flavour):
+    """The object file of every unit, where build(**flavour) puts them."""
+    objdir = _plan(**flavour)[2]
+    return [os.path.join(objdir, src + ".o") for src, _ in UNITS]
+
+
+def build(force=False, debug=False, verbose=True, dev=False, stamps=False):
+    out, common, objdir = _plan(debug, dev, stamps)
+    objs = object_files(debug=debug, dev=dev, stamps=stamps)
+    if not force and up_to_date(out):
+        if verbose:
+            print(f"[build] {out} is up to date")
+        return out
     os.makedirs(objdir, exist_ok=True)
-    objs, procs = [], []
-    for src, extra in UNITS:
+    procs = []
+    for (src, extra), obj in zip(UNITS, objs):
         path = os.path.join(SRC, src)
-        obj = os.path.join(objdir, src + ".o")
-        objs.append(obj)
         if not force and os.path.exists(obj) and all(
                 os.path.getmtime(d) <= os.path.getmtime(obj) for d in unit_deps(path)):
             continue
@@ -119,6 +136,11 @@ if __name__ == "__main__":
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--dev", action="store_true")
     ap.add_argument("--stamps", action="store_true", help="diagnostic build with in-kernel cycle stamps")
+    ap.add_argument("--list-units", action="store_true", help="print `source<TAB>extra flags` per unit and exit")
     a = ap.parse_args()
+    if a.list_units:
+        for src, extra in UNITS:
+            print(f"{src}\t{' '.join(extra)}")
+        sys.exit(0)
     build(a.force, a.debug, dev=a.dev, stamps=a.stamps)
     sys.exit(0)

@@ -211,7 +211,7 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
                 const void* bt, int64_t ldb, const float* bias, void* c, int64_t ldc,
                 int32_t epilogue, const void* aux, int64_t ldaux, void* c2);
 /* Which kernel sae_gemm_nt runs for a shape (host-only, no device needed): the round-5 routing
-   rule by tile fill and reduction depth (capi.hip, g8x_route / g8_route). */
+   rule by tile fill and reduction depth (gemm.hip, nt_plan: g8x_route / g8_route). */
 #define SAE_NT_ROUTE_NONE 0           /* shape not supported: sae_gemm_nt returns SAE_EUNSUPPORTED */
 #define SAE_NT_ROUTE_TILE128 1        /* 128-row tiles (gemm_nt_kernel), K % 64 == 0 */
 #define SAE_NT_ROUTE_TILE128_KTAIL 2  /* 128-row tiles, K % 8 == 0 with a partial last K stage */

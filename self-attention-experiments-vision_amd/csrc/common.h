@@ -59,7 +59,7 @@ __device__ __forceinline__ f32x16 zero16() { return f32x16{}; }
 // In-kernel cycle stamps (diagnostic build only: build.py --stamps defines SAE_STAMPS; the
 // release library compiles SAE_STAMP to nothing).  Lane 0 of every wave records the shader clock
 // (s_memtime) at slot `slot` of its (block, wave) record with a plain vector store; the host reads
-// the table back through sae_dev_stamps (capi.hip).  cdna_hip_programming.md §7 "In-kernel stamps".
+// the table back through sae_dev_stamps (attn.hip).  cdna_hip_programming.md §7 "In-kernel stamps".
 #ifdef SAE_STAMPS
 constexpr int kStampSlots = 32, kStampWaves = 16, kStampRecs = 1 << 22;
 __device__ unsigned long long g_sae_stamps[kStampRecs];

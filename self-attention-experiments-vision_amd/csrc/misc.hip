@@ -1,0 +1,368 @@
+// misc.hip -- the rest of the C ABI: residual add + LayerNorm (ln.h), the encoder input tokens
+// (tokens.h), the smoothed cross-entropy (loss.h), AdamW (adamw.h), the stream utilities of
+// bench.py, and the library's error string and version.
+#include "ln.h"
+#include "loss.h"
+#include "tokens.h"
+#include "adamw.h"
+#include "host.h"
+
+using namespace sae;
+
+thread_local std::string sae::g_err;
+
+namespace {
+
+// ------------------------------------------------------------ residual add + LayerNorm
+// rows per wave: with the rows software-pipelined (ln.h) fewer, longer-lived waves win -- 2048 / 1024
+// -> 1024 / 512 workgroups: DeiT-S step 8.220 -> 8.174 ms same box (profiles/r05ac_ln_grid_ab.txt;
+// before the pipelining, 512 backward workgroups were slower: too few rows in flight)
+int ln_fwd_blocks(int M) { return std::max(1, std::min((M + 3) / 4, 1024)); }
+int ln_bwd_blocks(int M) { return std::max(1, std::min((M + 3) / 4, 512)); }
+
+int ln_check(int32_t M, int32_t C) {
+  if (M < 1 || C < 4) return fail(SAE_EINVAL, "layernorm: M (%d) and C (%d) must be >= 1 / >= 4", M, C);
+  if (C % 4 || C > 4 * 64 * kLnMaxV)
+    return fail(SAE_EUNSUPPORTED, "layernorm: C (%d) must be a multiple of 4 and <= %d", C, 4 * 64 * kLnMaxV);
+  return SAE_OK;
+}
+
+int ln_fwd_impl(void* stream, int32_t M, int32_t C, const float* x, const void* delta, float* xout,
+                const float* gamma, const float* beta, void* y, float* mean, float* rstd, float eps,
+                const float* lsc, const float* rsc, int32_t rpb) {
+  if (int rc = ln_check(M, C)) return rc;
+  if (!x || !gamma || !beta || !y || !mean || !rstd) return fail(SAE_EINVAL, "layernorm_fwd: NULL argument");
+  if ((delta == nullptr) != (xout == nullptr))
+    return fail(SAE_EINVAL, "layernorm_fwd: delta and xout must both be given or both be NULL");
+  if (!aligned16(x) || !aligned16(xout) || !aligned16(gamma) || !aligned16(beta) || ((uintptr_t)delta & 7) ||
+      ((uintptr_t)y & 7))
+    return fail(SAE_EINVAL, "layernorm_fwd: x/xout/gamma/beta need 16-byte, delta/y 8-byte alignment");
+  LnArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.delta = reinterpret_cast<const __bf16*>(delta);
+  a.xout = xout;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.y = reinterpret_cast<__bf16*>(y);
+  a.mean = mean;
+  a.rstd = rstd;
+  a.M = M;
+  a.C = C;
+  a.eps = eps;
+  a.lsc = lsc;
+  a.rsc = rsc;
+  a.rpb = rpb > 0 ? rpb : 1;
+  int lnb = ln_fwd_blocks(M);
+  if (int v = dev_knob("SAE_LN_FWD_BLOCKS")) lnb = std::max(1, std::min((M + 3) / 4, v));
+  void (*const fn[4])(LnArgs) = {ln_fwd_kernel<1>, ln_fwd_kernel<2>, ln_fwd_kernel<3>, ln_fwd_kernel<4>};
+  const int nv = (C / 4 + 63) / 64;   // 1 .. kLnMaxV (ln_check)
+  return launch("layernorm_fwd", fn[nv - 1], (long long)lnb, dim3(256), 0, (hipStream_t)stream, a);
+}
+
+int ln_bwd_impl(void* stream, int32_t M, int32_t C, const float* x, const float* mean, const float* rstd,
+                const float* gamma, const void* dy, const float* dxin, float* dx, void* ddelta,
+                float* dgamma, float* dbeta, void* workspace, const void* delta, const float* lsc,
+                const float* rsc, int32_t rpb, float* dlsc) {
+  if (int rc = ln_check(M, C)) return rc;
+  if (!x || !mean || !rstd || !gamma || !dy || !dx || !dgamma || !dbeta || !workspace)
+    return fail(SAE_EINVAL, "layernorm_bwd: NULL argument");
+  if (!aligned16(x) || !aligned16(dxin) || !aligned16(dx) || !aligned16(gamma) || !aligned16(workspace) ||
+      ((uintptr_t)dy & 7) || ((uintptr_t)ddelta & 7))
+    return fail(SAE_EINVAL, "layernorm_bwd: x/dxin/dx/gamma/workspace need 16-byte, dy/ddelta 8-byte alignment");
+  LnArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.mean = const_cast<float*>(mean);
+  a.rstd = const_cast<float*>(rstd);
+  a.gamma = gamma;
+  a.dy = reinterpret_cast<const __bf16*>(dy);
+  a.dxin = dxin;
+  a.dx = dx;
+  a.ddelta = reinterpret_cast<__bf16*>(ddelta);
+  a.part = reinterpret_cast<float*>(workspace);
+  a.dgamma = dgamma;
+  a.dbeta = dbeta;
+  a.M = M;
+  a.C = C;
+  a.nblk = ln_bwd_blocks(M);
+  if (int v = dev_knob("SAE_LN_BWD_BLOCKS")) a.nblk = std::max(1, std::min(a.nblk, v));   // (workspace: <= default)
+  a.delta = reinterpret_cast<const __bf16*>(delta);
+  a.lsc = lsc;
+  a.rsc = rsc;
+  a.rpb = rpb > 0 ? rpb : 1;
+  a.dlsc = dlsc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool sc = lsc != nullptr;   // the scaled form: three partial rows (dgamma, dbeta, dlayerscale)
+  void (*const fn[4][2])(LnArgs) = {{ln_bwd_kernel<1, 2>, ln_bwd_kernel<1, 3>}, {ln_bwd_kernel<2, 2>, ln_bwd_kernel<2, 3>},
+                                    {ln_bwd_kernel<3, 2>, ln_bwd_kernel<3, 3>}, {ln_bwd_kernel<4, 2>, ln_bwd_kernel<4, 3>}};
+  const int nv = (C / 4 + 63) / 64;   // 1 .. kLnMaxV (ln_check)
+  if (int rc = launch("layernorm_bwd", fn[nv - 1][sc], (long long)a.nblk, dim3(256), 0, st, a)) return rc;
+  const long long rg = ((sc ? 3 : 2) * (C / 4) + kLnRedCols - 1) / kLnRedCols;
+  return launch("layernorm_bwd_reduce", sc ? ln_bwd_reduce_kernel<3> : ln_bwd_reduce_kernel<2>, rg, dim3(256), 0, st, a);
+}
+
+// ------------------------------------------------------------------ encoder input tokens
+int tokens_check(int32_t B, int32_t L, int32_t E) {
+  if (B < 1 || L < 1 || E < 4 || E % 4 || E > 4096)
+    return fail(SAE_EINVAL, "tokens: B %d, L %d, E %d (E a multiple of 4, <= 4096)", B, L, E);
+  return 0;
+}
+
+// ------------------------------------------------------------------ training loss
+int ce_check(int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype, const int64_t* labels) {
+  if (rows < 1 || rows > SAE_CE_MAX_ROWS || classes < 1 || ld < classes)
+    return fail(SAE_EINVAL, "smoothed_ce: rows %d (1..%d), classes %d, ld %lld", rows, SAE_CE_MAX_ROWS, classes,
+                (long long)ld);
+  if (dtype != SAE_DTYPE_BF16 && dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "smoothed_ce: bad dtype %d", dtype);
+  if (!logits || !labels) return fail(SAE_EINVAL, "smoothed_ce: NULL logits / labels");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sae_layernorm_fwd(void* stream, int32_t M, int32_t C, const float* x, const void* delta, float* xout,
+                      const float* gamma, const float* beta, void* y, float* mean, float* rstd, float eps) {
+  return ln_fwd_impl(stream, M, C, x, delta, xout, gamma, beta, y, mean, rstd, eps, nullptr, nullptr, 1);
+}
+
+int sae_layernorm_fwd_scaled(void* stream, int32_t M, int32_t C, const float* x, const void* delta, float* xout,
+                             const float* gamma, const float* beta, void* y, float* mean, float* rstd, float eps,
+                             const float* layerscale, const float* rowscale, int32_t rows_per_sample) {
+  if (!delta || !layerscale) return fail(SAE_EINVAL, "layernorm_fwd_scaled: delta and layerscale are required");
+  if (rowscale && (rows_per_sample < 1 || M % rows_per_sample))
+    return fail(SAE_EINVAL, "layernorm_fwd_scaled: rows_per_sample (%d) must divide M (%d)", rows_per_sample, M);
+  if (!aligned16(layerscale)) return fail(SAE_EINVAL, "layernorm_fwd_scaled: layerscale needs 16-byte alignment");
+  return ln_fwd_impl(stream, M, C, x, delta, xout, gamma, beta, y, mean, rstd, eps, layerscale, rowscale,
+                     rows_per_sample);
+}
+
+size_t sae_layernorm_bwd_workspace_bytes(int32_t M, int32_t C) {
+  if (M < 1 || C < 1) return 0;
+  return (size_t)ln_bwd_blocks(M) * 3 * C * sizeof(float);   // room for the scaled form
+}
+
+int sae_layernorm_bwd(void* stream, int32_t M, int32_t C, const float* x, const float* mean, const float* rstd,
+                      const float* gamma, const void* dy, const float* dxin, float* dx, void* ddelta, float* dgamma,
+                      float* dbeta, void* workspace) {
+  return ln_bwd_impl(stream, M, C, x, mean, rstd, gamma, dy, dxin, dx, ddelta, dgamma, dbeta, workspace, nullptr,
+                     nullptr, nullptr, 1, nullptr);
+}
+
+int sae_layernorm_bwd_scaled(void* stream, int32_t M, int32_t C, const float* x, const float* mean,
+                             const float* rstd, const float* gamma, const void* dy, const float* dxin, float* dx,
+                             void* ddelta, float* dgamma, float* dbeta, void* workspace, const void* delta,
+                             const float* layerscale, const float* rowscale, int32_t rows_per_sample,
+                             float* dlayerscale) {
+  if (!delta || !layerscale || !dlayerscale)
+    return fail(SAE_EINVAL, "layernorm_bwd_scaled: delta, layerscale and dlayerscale are required");
+  if (rowscale && (rows_per_sample < 1 || M % rows_per_sample))
+    return fail(SAE_EINVAL, "layernorm_bwd_scaled: rows_per_sample (%d) must divide M (%d)", rows_per_sample, M);
+  if (!aligned16(layerscale) || ((uintptr_t)delta & 7))
+    return fail(SAE_EINVAL, "layernorm_bwd_scaled: layerscale needs 16-byte, delta 8-byte alignment");
+  return ln_bwd_impl(stream, M, C, x, mean, rstd, gamma, dy, dxin, dx, ddelta, dgamma, dbeta, workspace, delta,
+                     layerscale, rowscale, rows_per_sample, dlayerscale);
+}
+
+int sae_tokens_fwd(void* stream, int32_t B, int32_t L, int32_t E, const void* tokens, const float* cls,
+                   const float* pos, float* x) {
+  if (int rc = tokens_check(B, L, E)) return rc;
+  if (!tokens || !cls || !pos || !x) return fail(SAE_EINVAL, "tokens_fwd: NULL argument");
+  if (!aligned16(cls) || !aligned16(pos) || !aligned16(x) || ((uintptr_t)tokens & 7))
+    return fail(SAE_EINVAL, "tokens_fwd: cls / pos / x need 16-byte, tokens 8-byte alignment");
+  const long long total = (long long)B * (L + 1) * (E / 4);
+  return launch("tokens_fwd", tokens_fwd_kernel, std::min<long long>((total + 255) / 256, 8192), dim3(256), 0,
+                (hipStream_t)stream, reinterpret_cast<const __bf16*>(tokens), cls, pos, x, B, L, E);
+}
+
+int sae_tokens_bwd(void* stream, int32_t B, int32_t L, int32_t E, const float* dx, void* dtokens, float* dcls,
+                   float* dpos) {
+  if (int rc = tokens_check(B, L, E)) return rc;
+  if (!dx || !dtokens || !dpos) return fail(SAE_EINVAL, "tokens_bwd: NULL argument");
+  if (!aligned16(dx) || !aligned16(dpos) || (dcls && !aligned16(dcls)) || ((uintptr_t)dtokens & 7))
+    return fail(SAE_EINVAL, "tokens_bwd: dx / dcls / dpos need 16-byte, dtokens 8-byte alignment");
+  const int E4 = E / 4;
+  const int G = std::max(1, std::min(B, 512 / E4));
+  return launch("tokens_bwd", tokens_bwd_kernel, (long long)L + 1, dim3((unsigned)(G * E4)), (size_t)G * E4 * 16,
+                (hipStream_t)stream, dx, reinterpret_cast<__bf16*>(dtokens), dcls, dpos, B, L, E);
+}
+
+int sae_smoothed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
+                        int32_t dtype, const int64_t* labels, float alpha, float* lse, float* row_loss, float* loss) {
+  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
+  if (!lse || !row_loss || !loss) return fail(SAE_EINVAL, "smoothed_ce_fwd: NULL lse / row_loss / loss");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = dtype == SAE_DTYPE_BF16
+                     ? launch("smoothed_ce_fwd", smoothed_ce_fwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
+                              reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, classes, alpha, lse, row_loss)
+                     : launch("smoothed_ce_fwd", smoothed_ce_fwd_kernel<float>, (long long)rows, dim3(256), 0, st,
+                              reinterpret_cast<const float*>(logits), (long long)ld, labels, classes, alpha, lse, row_loss);
+  if (rc) return rc;
+  return launch("smoothed_ce_mean", smoothed_ce_mean_kernel, 1LL, dim3(256), 0, st, row_loss, rows, loss);
+}
+
+int sae_smoothed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
+                        int32_t dtype, const int64_t* labels, float alpha, const float* lse,
+                        const float* grad_loss, void* dlogits, int64_t ldd) {
+  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
+  if (!lse || !grad_loss || !dlogits || ldd < classes)
+    return fail(SAE_EINVAL, "smoothed_ce_bwd: NULL lse / grad_loss / dlogits or ldd < classes");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SAE_DTYPE_BF16)
+    return launch("smoothed_ce_bwd", smoothed_ce_bwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
+                  reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, rows, classes, alpha, lse, grad_loss,
+                  reinterpret_cast<__bf16*>(dlogits), (long long)ldd);
+  return launch("smoothed_ce_bwd", smoothed_ce_bwd_kernel<float>, (long long)rows, dim3(256), 0, st,
+                reinterpret_cast<const float*>(logits), (long long)ld, labels, rows, classes, alpha, lse, grad_loss,
+                reinterpret_cast<float*>(dlogits), (long long)ldd);
+}
+
+// ---------------------------------------------------------------------------------- AdamW
+static_assert(sizeof(sae_adamw_chunk) == sizeof(AdamwChunk) && SAE_ADAMW_CHUNK == kAdamwChunk,
+              "sae_adamw_chunk mirrors AdamwChunk");
+
+int sae_adamw_plan(int32_t n_items, float* const* p, const float* const* g, float* const* m, float* const* v,
+                   const int64_t* n, sae_adamw_chunk* chunks, int64_t max_chunks, int64_t* n_chunks) {
+  if (n_items < 0 || !n_chunks || (n_items > 0 && (!p || !g || !m || !v || !n)))
+    return fail(SAE_EINVAL, "adamw_plan: bad arguments");
+  int64_t k = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i])))
+      return fail(SAE_EINVAL, "adamw_plan: item %d invalid", i);
+    for (int64_t off = 0; off < n[i]; off += SAE_ADAMW_CHUNK, ++k) {
+      if (k < max_chunks && chunks) {
+        sae_adamw_chunk& c = chunks[k];
+        c.p = p[i] + off;
+        c.g = g[i] + off;
+        c.m = m[i] + off;
+        c.v = v[i] + off;
+        c.n = (int32_t)std::min<int64_t>(SAE_ADAMW_CHUNK, n[i] - off);
+        c.vec = c.n == SAE_ADAMW_CHUNK && aligned16(c.p) && aligned16(c.g) && aligned16(c.m) && aligned16(c.v);
+      }
+    }
+  }
+  *n_chunks = k;
+  if (k > max_chunks) return fail(SAE_EINVAL, "adamw_plan: %lld chunks > capacity %lld", (long long)k,
+                                  (long long)max_chunks);
+  return ok();
+}
+
+int sae_adamw_step(void* stream, int64_t n_chunks, const sae_adamw_chunk* chunks, int32_t* step, float lr,
+                   float beta1, float beta2, float eps, float weight_decay) {
+  if (n_chunks < 0 || n_chunks >= (1LL << 31) || (n_chunks > 0 && !chunks) || !step)
+    return fail(SAE_EINVAL, "adamw_step: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch("adamw_tick", adamw_tick_kernel, 1LL, dim3(64), 0, st, step)) return rc;
+  if (n_chunks == 0) return ok();
+  return launch("adamw", adamw_kernel, (long long)n_chunks, dim3(256), 0, st, reinterpret_cast<const AdamwChunk*>(chunks),
+                step, lr, beta1, beta2, eps, weight_decay);
+}
+
+static_assert(sizeof(sae_adamw_cast_tile) == sizeof(AdamwCastTile), "sae_adamw_cast_tile mirrors AdamwCastTile");
+
+int sae_adamw_cast_plan(int32_t n_items, float* const* p, const float* const* g, float* const* m,
+                        float* const* v, const int32_t* K, const int32_t* N, void* const* w16, const int32_t* ld16,
+                        void* const* wt16, const int32_t* ldT, const int32_t* col0, sae_adamw_cast_tile* tiles,
+                        int64_t max_tiles, int64_t* n_tiles) {
+  if (n_items < 0 || !n_tiles || (n_items > 0 && (!p || !g || !m || !v || !K || !N || !col0)))
+    return fail(SAE_EINVAL, "adamw_cast_plan: bad arguments");
+  const auto a8 = [](const void* q) { return ((uintptr_t)q & 7) == 0; };
+  int64_t k = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    void* o16 = w16 ? w16[i] : nullptr;
+    void* oT = wt16 ? wt16[i] : nullptr;
+    const int32_t l16 = ld16 ? ld16[i] : 0, lT = ldT ? ldT[i] : 0;
+    if (!p[i] || !g[i] || !m[i] || !v[i] || K[i] < 1 || N[i] < 1 || col0[i] < 0 || (!o16 && !oT) ||
+        (o16 && l16 < col0[i] + N[i]) || (oT && lT < K[i]))
+      return fail(SAE_EINVAL, "adamw_cast_plan: item %d invalid (K %d N %d col0 %d ld16 %d ldT %d)", i, K[i], N[i],
+                  col0[i], l16, lT);
+    if (K[i] % 4 || N[i] % 4 || col0[i] % 4 || !aligned16(p[i]) || !aligned16(g[i]) || !aligned16(m[i]) ||
+        !aligned16(v[i]) || (o16 && (l16 % 4 || !a8(o16))) || (oT && (lT % 4 || !a8(oT))))
+      return fail(SAE_EUNSUPPORTED, "adamw_cast_plan: item %d needs K/N/col0/ld multiples of 4 and aligned buffers",
+                  i);
+    for (int32_t k0 = 0; k0 < K[i]; k0 += 64)
+      for (int32_t n0 = 0; n0 < N[i]; n0 += 64, ++k) {
+        if (k < max_tiles && tiles) {
+          sae_adamw_cast_tile& t = tiles[k];
+          t.p = p[i];
+          t.g = g[i];
+          t.m = m[i];
+          t.v = v[i];
+          t.w16 = o16;
+          t.wt16 = oT;
+          t.K = K[i];
+          t.N = N[i];
+          t.ld16 = l16;
+          t.ldT = lT;
+          t.col0 = col0[i];
+          t.k0 = k0;
+          t.n0 = n0;
+          t.pad = 0;
+        }
+      }
+  }
+  *n_tiles = k;
+  if (k > max_tiles)
+    return fail(SAE_EINVAL, "adamw_cast_plan: %lld tiles > capacity %lld", (long long)k, (long long)max_tiles);
+  return ok();
+}
+
+int sae_adamw_step_cast(void* stream, int64_t n_chunks, const sae_adamw_chunk* chunks, int64_t n_tiles,
+                        const sae_adamw_cast_tile* tiles, int32_t* step, float lr, float beta1, float beta2, float eps,
+                        float weight_decay) {
+  if (n_chunks < 0 || n_tiles < 0 || n_chunks + n_tiles >= (1LL << 31) || (n_chunks > 0 && !chunks) ||
+      (n_tiles > 0 && !tiles) || !step)
+    return fail(SAE_EINVAL, "adamw_step_cast: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch("adamw_tick", adamw_tick_kernel, 1LL, dim3(64), 0, st, step)) return rc;
+  if (n_chunks + n_tiles == 0) return ok();
+  return launch("adamw_cast", adamw_cast_kernel, (long long)(n_chunks + n_tiles), dim3(256), 0, st,
+                reinterpret_cast<const AdamwChunk*>(chunks), (int)n_chunks, reinterpret_cast<const AdamwCastTile*>(tiles),
+                step, lr, beta1, beta2, eps, weight_decay);
+}
+
+// ------------------------------------------------------------------------ stream utilities
+// bench.py --emulate-rccl: workgroups that hold their CU's slots (waves, LDS) for `ticks` of the
+// 100 MHz real-time counter while sleeping -- the CU footprint of an RCCL ring channel
+__global__ void occupy_cus_kernel(long long ticks) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const long long t0 = __builtin_amdgcn_s_memrealtime();
+  if (threadIdx.x == 0) lds[0] = 0;
+  while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
+}
+
+__global__ void flag_bump_kernel(unsigned* flag) {
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+int sae_occupy_cus(void* stream, int32_t workgroups, int32_t threads, int32_t lds_bytes, float usec) {
+  if (workgroups < 1 || threads < 64 || threads > 1024 || lds_bytes < 0 || lds_bytes > 160 * 1024 || !(usec >= 0.f))
+    return fail(SAE_EINVAL, "occupy_cus: bad arguments (%d workgroups, %d threads, %d B LDS, %g us)", workgroups,
+                threads, lds_bytes, (double)usec);
+  return launch("occupy_cus", occupy_cus_kernel, (long long)workgroups, dim3((unsigned)threads), (size_t)lds_bytes,
+                (hipStream_t)stream, (long long)(usec * 100.f));
+}
+
+int sae_flag_bump(void* stream, uint32_t* flags, int32_t index) {
+  if (!flags || index < 0) return fail(SAE_EINVAL, "flag_bump: flags must be non-NULL and index >= 0");
+  return launch("flag_bump", flag_bump_kernel, 1LL, dim3(64), 0, (hipStream_t)stream, (unsigned*)flags + index);
+}
+
+int sae_stream_wait_flag(void* stream, const uint32_t* flag, uint32_t value) {
+  if (!flag || ((uintptr_t)flag & 3)) return fail(SAE_EINVAL, "stream_wait_flag: flag must be a non-NULL 4-byte-aligned pointer");
+  const hipError_t e = hipStreamWaitValue32((hipStream_t)stream, const_cast<uint32_t*>(flag), value,
+                                            hipStreamWaitValueGte, 0xffffffffu);
+  if (e != hipSuccess) return fail(SAE_EHIP, "hipStreamWaitValue32: %s", hipGetErrorString(e));
+  return ok();
+}
+
+// ------------------------------------------------------------------------------ the library
+const char* sae_last_error(void) { return g_err.c_str(); }
+
+int32_t sae_abi_version(void) { return SAE_ABI_VERSION; }
+
+const char* sae_build_info(void) { return "sae_attn gfx950 (" __DATE__ " " __TIME__ ")"; }
+
+}  // extern "C"

@@ -580,12 +580,3 @@ __global__ __launch_bounds__(256) void th_reduce_kernel(ThArgs a) {
 }
 
 }  // namespace sae
-
-// ---------------------------------------------------------------- launchers (capi.hip)
-struct sae_attn_desc;
-int th_fwd(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v, const float* th1,
-           const float* th2, void* o, float* lse, const sae::RopeTab* rope = nullptr);
-size_t th_bwd_workspace_bytes(const sae_attn_desc* d);
-int th_bwd(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v, const float* th1,
-           const float* th2, const float* lse, const void* dout, void* dq, void* dk, void* dv, float* dth1,
-           float* dth2, void* workspace, const sae::RopeTab* rope = nullptr);

@@ -1098,7 +1098,7 @@ FF_GELU_GRAD = os.environ.get("SAE_FF_GELU_GRAD", "1") != "0"   # (False: save h
 
 
 # Every bf16 forward / input-gradient projection whose widths are multiples of 8 runs on
-# sae_gemm_nt (round 5): the C ABI picks the kernel by tile fill and reduction depth (capi.hip,
+# sae_gemm_nt (round 5): the C ABI picks the kernel by tile fill and reduction depth (gemm.hip nt_plan,
 # g8x_route / g8_route: the persistent gemm8, the ping-pong gemm8x, or the 128-row kernel, which
 # also takes K not a multiple of 64).  That covers every width in create_model.py:6-215 (ViT-B/L,
 # DeiT, CaiT 192-768, CeiT, CvT 64/192/368/1024, TNT 24/40/384/640); tests/test_routing_cpu.py

@@ -268,7 +268,7 @@ def test_gemm8_strided(dev):
     assert torch.all(cw[:, :32] == 3.0) and torch.all(cw[:, 32 + N:] == 3.0)
 
 
-# Round 5 routing (capi.hip g8x_route / g8_route, sae_gemm_nt_route): K not a multiple of 64 on the
+# Round 5 routing (gemm.hip nt_plan: g8x_route / g8_route, sae_gemm_nt_route): K not a multiple of 64 on the
 # 128-row kernel's K-tail instances (CaiT-XXS/XS 288, CvT 368, TNT inner 24 / 40, their FF widths,
 # the classifier head's K = 1000 input gradient), and the ViT-L / CvT-W24 1024 / 4096 widths on
 # gemm8x.  Each case asserts which kernel the C ABI picked, so the test exercises that kernel.

@@ -1,6 +1,6 @@
 // Host-side AddressSanitizer run of the C ABI ("race detection / sanitizers":
 // the reference has none; this is the host half of the plan -- GPU ASan is not available on the
-// MI355X pool).  Built by tools/asan/build.sh with the host code of capi.hip instrumented
+// MI355X pool).  Built by tools/asan/build.sh with the host code of every unit instrumented
 // (-Xarch_host -fsanitize=address); needs no GPU.  It drives every host-only code path of the ABI
 // with exact-capacity heap tables, so any overrun of a caller buffer or a descriptor is caught:
 //   * the AdamW chunk / tile planners (host only: they write the tables the caller allocated), on
