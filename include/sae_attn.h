@@ -137,6 +137,36 @@ int sae_attn_bwd_rotary(void* stream, const sae_attn_desc* desc, const void* q, 
                         const float* sin_tab, const float* cos_tab, void* dq, void* dk, void* dv,
                         void* workspace);
 
+/* Attention-probability dropout (attention.py:54-58: nn.Dropout(rate = attn_dropout_rate) on the
+   softmax output before the AV product), regenerated from counters by forward and backward alike;
+   no mask is stored, and the mask does not depend on the kernel serving the call:
+     T        = clamp(lrintf(rate * 256), 0, 255),  keep probability pk = (256 - T) / 256
+     (k0, k1) = words 0, 1 of Philox4x32-10(counter (lo32(offset), hi32(offset), stream_id, 0),
+                                            key (lo32(seed), hi32(seed)))
+     W        = Philox4x32-10(counter (k >> 2, q >> 2, b * heads + h, 0), key (k0, k1))
+     keep(b, h, q, k) = ((W[q & 3] >> (8 * (k & 3))) & 0xff) >= T
+     o[q] = sum_k P[q, k] * keep / pk * v[k];  lse is that of the undropped scores.
+   rng points at device memory {seed, offset} (two uint64), read by the kernels, so a captured
+   graph replays with a fresh mask once sae_dropout_advance has bumped the offset on the stream.
+   stream_id tells the attention calls of one step apart; the backward passes the forward's.
+   The rate is quantised to n / 256 and the rescale uses exactly pk; a rate below 1 / 512 gives
+   T = 0, which means no dropout: the call is forwarded to sae_attn_fwd / sae_attn_bwd.
+   rate outside [0, 1) or NaN, or rng == NULL: SAE_EINVAL.  desc->flags != 0: SAE_EUNSUPPORTED (no
+   relative logits).  Otherwise the envelope is that of sae_attn_fwd / sae_attn_bwd. */
+int sae_attn_fwd_dropout(void* stream, const sae_attn_desc* desc, const void* q, const void* k,
+                         const void* v, void* o, float* lse, float rate, const uint64_t* rng,
+                         uint32_t stream_id);
+int sae_attn_bwd_dropout(void* stream, const sae_attn_desc* desc, const void* q, const void* k,
+                         const void* v, const void* o, const float* lse, const void* dout,
+                         void* dq, void* dk, void* dv,
+                         void* workspace /* sae_attn_bwd_workspace_bytes */, float rate,
+                         const uint64_t* rng, uint32_t stream_id);
+/* keep[b][h][q][k] as uint8 0 / 1 by the definition above: what the two entry points apply. */
+int sae_attn_dropout_mask(void* stream, int32_t batch, int32_t heads, int32_t seq_q, int32_t seq_k,
+                          float rate, const uint64_t* rng, uint32_t stream_id, uint8_t* keep);
+/* rng[1] += n on the stream (a one-thread kernel). */
+int sae_dropout_advance(void* stream, uint64_t* rng, uint64_t n);
+
 /* Talking-heads attention (attention.py:41-58 with talking_heads=True):
      S = scale q k^T ; S1[i] = sum_h th1[h,i] S[h] ; P = softmax(S1) ;
      P2[i] = sum_h th2[h,i] P[h] ; o = P2 v

@@ -59,6 +59,10 @@ _PROTOS = [
     ("sae_relpos_bias_bwd", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _S3, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _S3, _vp, _vp, _vp]),
     ("sae_rotary", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _S3, _vp, _S3, _vp, _vp, _i32]),
+    ("sae_attn_fwd_dropout", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 5 + [_f32, _vp, ctypes.c_uint32]),
+    ("sae_attn_bwd_dropout", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 10 + [_f32, _vp, ctypes.c_uint32]),
+    ("sae_attn_dropout_mask", _i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, ctypes.c_uint32, _vp]),
+    ("sae_dropout_advance", _i32, [_vp, _vp, ctypes.c_uint64]),
     ("sae_th_attn_fwd", _i32, [_vp, ctypes.POINTER(SaeAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("sae_th_attn_bwd_workspace_bytes", _sz, [ctypes.POINTER(SaeAttnDesc)]),
     ("sae_th_attn_bwd", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 13),

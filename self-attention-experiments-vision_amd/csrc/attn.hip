@@ -10,6 +10,36 @@
 #include "cls.h"
 #include "desc.h"
 
+namespace sae {
+
+// ------------------------------------------------------------------------ dropout: standalone kernels
+// keep[b][h][q][k] as uint8 0 / 1: one thread per element (a test and debugging aid)
+struct DropMaskArgs {
+  const unsigned long long* rng;
+  unsigned char* keep;
+  long long n;
+  int H, Nq, Nk;
+  unsigned stream_id, thr;
+};
+
+__global__ void dropout_mask_kernel(DropMaskArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const DropKey dk = drop_key(a.rng, a.stream_id);
+  const unsigned k = (unsigned)(i % a.Nk);
+  const long long t = i / a.Nk;
+  const unsigned q = (unsigned)(t % a.Nq);
+  const unsigned bh = (unsigned)(t / a.Nq);
+  a.keep[i] = drop_keep(dk, a.thr, bh, q, k) ? 1 : 0;
+}
+
+// offset += n on the stream (the next step's masks)
+__global__ void dropout_advance_kernel(unsigned long long* rng, unsigned long long n) {
+  if (threadIdx.x == 0) rng[1] += n;
+}
+
+}  // namespace sae
+
 using namespace sae;
 
 namespace {
@@ -66,11 +96,11 @@ template <typename T, int DP, bool VEC, bool REL> struct BwdL {
 
 // lean bf16 forward (fwd2.h): NW waves x 32 query rows per workgroup
 template <int DP, int NW, int MINW, bool LSUM, bool ROT = false, int NSU = DP / 16, bool REL = false,
-          bool FIX = false>
+          bool FIX = false, bool DROP = false>
 int fwd2_run(hipStream_t st, const AttnArgs& a) {
   const long long grid = (long long)((a.Nq + 32 * NW - 1) / (32 * NW)) * a.H * a.B;
   const size_t lds = 4 * (size_t)F2<DP>::TILE + (REL ? 2 * kRelImg : 0);
-  return launch("attn_fwd2", attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX>, grid, dim3(64 * NW), lds, st, a);
+  return launch("attn_fwd2", attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX, DROP>, grid, dim3(64 * NW), lds, st, a);
 }
 
 // BoTNet relative logits on the lean bf16 kernels: the table columns (Hs + Ws) fit the two extra
@@ -118,17 +148,85 @@ template <int DP, bool ROT = false> int bwd2_run_default(hipStream_t st, const A
 // (8 waves x 32 keys, two waves per SIMD); longer key ranges take the two-pass bwd2
 constexpr int kB3Keys = 256;
 
-template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16>
+template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16, bool DROP = false>
 int bwd3_run(hipStream_t st, const AttnArgs& a) {
   using C = B3<DP, NW, KPW>;
   static_assert(C::BK == kB3Keys, "bwd3 dispatch assumes 256-key blocks");
   if (a.Nk > C::BK) return fail(SAE_EINVAL, "bwd3: %d keys > %d", a.Nk, C::BK);
-  return launch("attn_bwd3", attn_bwd3_kernel<DP, NW, KPW, ROT, NSU>, (long long)a.H * a.B, dim3(64 * NW), C::LDS, st,
+  return launch("attn_bwd3", attn_bwd3_kernel<DP, NW, KPW, ROT, NSU, DROP>, (long long)a.H * a.B, dim3(64 * NW), C::LDS, st,
                 a);
 }
 
+// ------------------------------------------------------------------------------- dropout
+// Attention-probability dropout (dropout.h).  The v1 kernels' DROP instances cover the whole
+// envelope of the plain entry points with flags == 0 (fp32, unaligned strides or head_dim,
+// head_dim > 64, a single query row).
+struct DropCall {
+  const unsigned long long* rng;
+  unsigned stream_id, thr;
+};
+
+void fill_drop(AttnArgs& a, const DropCall& c) {
+  a.drop_rng = c.rng;
+  a.drop_stream = c.stream_id;
+  a.drop_thr = c.thr;
+  a.drop_inv = 256.f / (float)(256 - (int)c.thr);
+}
+
+// T = clamp(lrintf(rate * 256), 0, 255): a rate below 1 / 512 rounds to T = 0, no dropout
+int drop_check(const sae_attn_desc* d, float rate, const uint64_t* rng, unsigned* thr) {
+  if (!(rate >= 0.f && rate < 1.f)) return fail(SAE_EINVAL, "dropout rate %g is outside [0, 1)", (double)rate);
+  if (!rng) return fail(SAE_EINVAL, "dropout: rng must be non-NULL");
+  if (!d) return fail(SAE_EINVAL, "desc is NULL");
+  if (d->flags != 0)
+    return fail(SAE_EUNSUPPORTED, "dropout: flags 0x%x are not supported (no relative logits)", d->flags);
+  *thr = (unsigned)std::min(255L, std::max(0L, lrintf(rate * 256.f)));
+  return SAE_OK;
+}
+
+// the lean bf16 kernels' DROP instances: aligned strides, head_dim <= 64, more than one query row
+bool drop_lean(const sae_attn_desc* d, bool vec, int dp) {
+  return d->dtype == SAE_DTYPE_BF16 && vec && dp <= 64 && d->seq_q > 1;
+}
+
+template <typename T, int DP, bool VEC> struct FwdDropL {
+  static int run(hipStream_t st, const AttnArgs& a) {
+    const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
+    const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK);
+    return launch("attn_fwd_drop", attn_fwd_kernel<T, DP, VEC, false, true>, grid, dim3(256), lds, st, a);
+  }
+};
+
+template <typename T, int DP, bool VEC> struct BwdDropL {
+  static int run(hipStream_t st, const AttnArgs& a) {
+    {  // dQ (+ delta) first, as in BwdL
+      const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
+      const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK);
+      if (int rc = launch("attn_bwd_dq_drop", attn_bwd_dq_kernel<T, DP, VEC, false, true>, grid, dim3(256), lds, st, a))
+        return rc;
+    }
+    const long long grid = (long long)((a.Nk + kBKV - 1) / kBKV) * a.H * a.B;
+    const size_t lds = nbuf<T, DP>() * (2 * Img<T, DP>::bytes(kBQT) + 2 * kBQT * sizeof(float));
+    return launch("attn_bwd_dkdv_drop", attn_bwd_dkdv_kernel<T, DP, VEC, false, true>, grid, dim3(256), lds, st, a);
+  }
+};
+
+template <template <typename, int, bool> class L, typename... Args>
+int dispatch_drop(int dtype, int dp, bool vec, Args&&... args) {
+#define SAE_CASE(T, DPV) \
+  if (dp == DPV) return vec ? L<T, DPV, true>::run(args...) : L<T, DPV, false>::run(args...);
+  if (dtype == SAE_DTYPE_BF16) {
+    SAE_CASE(__bf16, 32) SAE_CASE(__bf16, 64) SAE_CASE(__bf16, 128)
+  } else {
+    SAE_CASE(float, 32) SAE_CASE(float, 64) SAE_CASE(float, 128)
+  }
+#undef SAE_CASE
+  return fail(SAE_EUNSUPPORTED, "no dropout kernel instance for dtype %d dp %d", dtype, dp);
+}
+
 int attn_fwd_impl(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v,
-                  const float* bias_h, const float* bias_w, void* o, float* lse, const RopeTab* rope) {
+                  const float* bias_h, const float* bias_w, void* o, float* lse, const RopeTab* rope,
+                  const DropCall* drop = nullptr) {
   int rc = validate(d, false);
   if (rc) return rc;
   if (!q || !k || !v || !o) return fail(SAE_EINVAL, "q/k/v/o must be non-NULL");
@@ -155,6 +253,17 @@ int attn_fwd_impl(void* stream, const sae_attn_desc* d, const void* q, const voi
     if (dp == 32) return fwd2_dispatch<32, true>(st, a);
     return fwd2_dispatch<64, true>(st, a);
   }
+  if (drop) {
+    fill_drop(a, *drop);
+    if (drop_lean(d, vec, dp)) {
+      // the lean forward's D <= 64 variant (VALU row sum, FIX) with the dropped P zeroed; at DP 64
+      // the Philox state does not fit three waves per SIMD (5 / 16 VGPRs spilled): two there
+      if (dp == 32) return fwd2_run<32, 4, 3, false, false, 2, false, true, true>(st, a);
+      if (d->head_dim <= 48) return fwd2_run<64, 4, 2, false, false, 3, false, true, true>(st, a);
+      return fwd2_run<64, 4, 2, false, false, 4, false, true, true>(st, a);
+    }
+    return dispatch_drop<FwdDropL>(d->dtype, dp, vec, st, a);
+  }
   if (var != 1 && vec && cls_ok(d)) return cls_run<false>(st, a);
   if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && !rel) {
     if (dp == 32) return fwd2_dispatch<32>(st, a);
@@ -172,7 +281,7 @@ int attn_fwd_impl(void* stream, const sae_attn_desc* d, const void* q, const voi
 int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v,
                   const void* o, const float* lse, const void* dout, const float* bias_h,
                   const float* bias_w, void* dq, void* dk, void* dv, float* dbias_h, float* dbias_w,
-                  void* workspace, const RopeTab* rope) {
+                  void* workspace, const RopeTab* rope, const DropCall* drop = nullptr) {
   int rc = validate(d, true);
   if (rc) return rc;
   if (!q || !k || !v || !o || !lse || !dout || !dq || !dk || !dv || !workspace)
@@ -208,6 +317,19 @@ int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, const voi
     if (a.Nk <= kB3Keys)
       return dp == 32 ? bwd3_run<32, 8, 1, true, 2>(st, a) : bwd3_run<64, 8, 1, true, 4>(st, a);
     return dp == 32 ? bwd2_run_default<32, true>(st, a) : bwd2_run_default<64, true>(st, a);
+  }
+  if (drop) {
+    fill_drop(a, *drop);
+    if (drop_lean(d, vec, dp)) {
+      if (a.Nk <= kB3Keys) {
+        if (dp == 32) return bwd3_run<32, 8, 1, false, 2, true>(st, a);
+        if (d->head_dim <= 48) return bwd3_run<64, 8, 1, false, 3, true>(st, a);
+        return bwd3_run<64, 8, 1, false, 4, true>(st, a);
+      }
+      if (dp == 32) return bwd2_run<32, 4, 2, 4, 2, false, false, true>(st, a);
+      return bwd2_run<64, 4, 2, 4, 2, false, false, true>(st, a);
+    }
+    return dispatch_drop<BwdDropL>(d->dtype, dp, vec, st, a);
   }
   if (var != 1 && vec && cls_ok(d)) return cls_run<true>(st, a);
   if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && !rel) {
@@ -302,6 +424,53 @@ int sae_attn_bwd_rotary(void* stream, const sae_attn_desc* d, const void* q, con
   const RopeTab t = make_rope(d, sin_tab, cos_tab);
   return attn_bwd_impl(stream, d, q, k, v, o, lse, dout, nullptr, nullptr, dq, dk, dv, nullptr, nullptr, workspace,
                        &t);
+}
+
+// --------------------------------------------------------------------------------- dropout
+int sae_attn_fwd_dropout(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v, void* o,
+                         float* lse, float rate, const uint64_t* rng, uint32_t stream_id) {
+  unsigned thr = 0;
+  if (int rc = drop_check(d, rate, rng, &thr)) return rc;
+  if (thr == 0) return attn_fwd_impl(stream, d, q, k, v, nullptr, nullptr, o, lse, nullptr);
+  const DropCall c{reinterpret_cast<const unsigned long long*>(rng), stream_id, thr};
+  return attn_fwd_impl(stream, d, q, k, v, nullptr, nullptr, o, lse, nullptr, &c);
+}
+
+int sae_attn_bwd_dropout(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v,
+                         const void* o, const float* lse, const void* dout, void* dq, void* dk, void* dv,
+                         void* workspace, float rate, const uint64_t* rng, uint32_t stream_id) {
+  unsigned thr = 0;
+  if (int rc = drop_check(d, rate, rng, &thr)) return rc;
+  if (thr == 0)
+    return attn_bwd_impl(stream, d, q, k, v, o, lse, dout, nullptr, nullptr, dq, dk, dv, nullptr, nullptr, workspace,
+                         nullptr);
+  const DropCall c{reinterpret_cast<const unsigned long long*>(rng), stream_id, thr};
+  return attn_bwd_impl(stream, d, q, k, v, o, lse, dout, nullptr, nullptr, dq, dk, dv, nullptr, nullptr, workspace,
+                       nullptr, &c);
+}
+
+int sae_attn_dropout_mask(void* stream, int32_t B, int32_t H, int32_t Nq, int32_t Nk, float rate, const uint64_t* rng,
+                          uint32_t stream_id, uint8_t* keep) {
+  if (!(rate >= 0.f && rate < 1.f)) return fail(SAE_EINVAL, "dropout rate %g is outside [0, 1)", (double)rate);
+  if (!rng || !keep) return fail(SAE_EINVAL, "dropout: rng and keep must be non-NULL");
+  if (B < 1 || H < 1 || Nq < 1 || Nk < 1) return fail(SAE_EINVAL, "dropout mask sizes must be >= 1");
+  DropMaskArgs a;
+  memset(&a, 0, sizeof a);
+  a.rng = reinterpret_cast<const unsigned long long*>(rng);
+  a.keep = keep;
+  a.n = (long long)B * H * Nq * Nk;
+  a.H = H;
+  a.Nq = Nq;
+  a.Nk = Nk;
+  a.stream_id = stream_id;
+  a.thr = (unsigned)std::min(255L, std::max(0L, lrintf(rate * 256.f)));
+  return launch("dropout_mask", dropout_mask_kernel, blocks256(a.n), dim3(256), 0, (hipStream_t)stream, a);
+}
+
+int sae_dropout_advance(void* stream, uint64_t* rng, uint64_t n) {
+  if (!rng) return fail(SAE_EINVAL, "dropout: rng must be non-NULL");
+  return launch("dropout_advance", dropout_advance_kernel, 1LL, dim3(64), 0, (hipStream_t)stream,
+                reinterpret_cast<unsigned long long*>(rng), (unsigned long long)n);
 }
 
 // ------------------------------------------------------------------------- relative logits

@@ -21,6 +21,7 @@
 //                  dK^T += Q^T dS.
 #pragma once
 #include "common.h"
+#include "dropout.h"
 
 namespace sae {
 
@@ -45,6 +46,11 @@ struct AttnArgs {
   float scale;
   int rel_h, rel_w, rel_magic;
   RopeTab rope;     // rotary tables (the ROT kernel instances), rope.sin == nullptr otherwise
+  // attention-probability dropout (the DROP kernel instances, dropout.h): device state
+  // {seed, offset}, the call's stream id, the byte threshold T and 1 / pk = 256 / (256 - T)
+  const unsigned long long* drop_rng;
+  unsigned drop_stream, drop_thr;
+  float drop_inv;
 };
 
 constexpr int kBQ = 128;   // query rows per forward / dq workgroup (4 waves x 32)
@@ -69,11 +75,14 @@ constexpr int fwd_lds_bytes_static() {
 // exponentiated (T13 safe order).
 template <typename T> struct LazyThr { static constexpr float v = sizeof(T) == 2 ? 8.f : 0.f; };
 
-template <typename T, int DP, bool REL, bool MASK>
+// DROP: the dropped P are zeroed after the row sum (l is the sum of the undropped P) and before
+// they feed the AV product; the kernel folds 1 / pk into the final 1 / l.
+template <typename T, int DP, bool REL, bool MASK, bool DROP = false>
 __device__ __forceinline__ void fwd_tile(const char* ldsK, const char* ldsV, const typename MF<T>::frag* qf,
                                          f32x16* acco, float& m, float& l, int key0, int Nk, float sl2,
                                          const float* wbrow, int rel_h, int rel_w, int rel_magic, int h, int r32,
-                                         int lane) {
+                                         int lane, const DropKey* dk = nullptr, unsigned thr = 0, unsigned bh = 0,
+                                         int q = 0) {
   using M = MF<T>;
   using I = Img<T, DP>;
   constexpr int NS = DP / M::KSTEP, NP = 32 / M::KSTEP, NT = DP / 32;
@@ -131,6 +140,15 @@ __device__ __forceinline__ void fwd_tile(const char* ldsK, const char* ldsV, con
     }
   }
   l += ls;
+  if constexpr (DROP) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (u == 1 && !two) continue;
+      const unsigned keep = drop_keep16<true>(*dk, thr, bh, q, (key0 + 32 * u + 4 * h) >> 2);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sacc[u][r] = ((keep >> r) & 1u) ? sacc[u][r] : 0.f;
+    }
+  }
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     if (u == 1 && !two) continue;
@@ -143,8 +161,8 @@ __device__ __forceinline__ void fwd_tile(const char* ldsK, const char* ldsV, con
   }
 }
 
-template <typename T, int DP, bool VEC, bool REL>
-__global__ __launch_bounds__(256, DP >= 128 ? 1 : ((DP == 64 && sizeof(T) == 2 && !REL && VEC) ? 3 : 2)) void attn_fwd_kernel(AttnArgs a) {
+template <typename T, int DP, bool VEC, bool REL, bool DROP = false>
+__global__ __launch_bounds__(256, DP >= 128 ? 1 : ((DP == 64 && sizeof(T) == 2 && !REL && VEC && !DROP) ? 3 : 2)) void attn_fwd_kernel(AttnArgs a) {
   using M = MF<T>;
   using I = Img<T, DP>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -197,6 +215,9 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : ((DP == 64 && sizeof(T) == 2 &
   const float sl2 = a.scale * kLog2e;
   const int nkt = (a.Nk + kBK - 1) / kBK;
   const int nfull = a.Nk / kBK;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
 
   Stage<T, DP, kBK, VEC> kst, vst;
   const __amdgpu_buffer_rsrc_t rk = row_rsrc(K, a.Nk, a.ks[1]);
@@ -227,11 +248,11 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : ((DP == 64 && sizeof(T) == 2 &
     }
     if (active) {                              // waves with no valid query row only stage + sync
       if (kt < nfull)
-        fwd_tile<T, DP, REL, false>(ldsK, ldsV, qf, acco, m, l, kt * kBK, a.Nk, sl2, wbrow, a.rel_h, a.rel_w,
-                                    a.rel_magic, h, r32, lane);
+        fwd_tile<T, DP, REL, false, DROP>(ldsK, ldsV, qf, acco, m, l, kt * kBK, a.Nk, sl2, wbrow, a.rel_h, a.rel_w,
+                                          a.rel_magic, h, r32, lane, &dkey, a.drop_thr, bh, q);
       else
-        fwd_tile<T, DP, REL, true>(ldsK, ldsV, qf, acco, m, l, kt * kBK, a.Nk, sl2, wbrow, a.rel_h, a.rel_w,
-                                   a.rel_magic, h, r32, lane);
+        fwd_tile<T, DP, REL, true, DROP>(ldsK, ldsV, qf, acco, m, l, kt * kBK, a.Nk, sl2, wbrow, a.rel_h, a.rel_w,
+                                         a.rel_magic, h, r32, lane, &dkey, a.drop_thr, bh, q);
     }
     if (more) {                               // the other buffer was last read before the previous barrier
       if (nbuf<T, DP>() == 1) __syncthreads();
@@ -243,7 +264,7 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : ((DP == 64 && sizeof(T) == 2 &
   }
 
   l += __shfl_xor(l, 32);
-  const float inv = 1.f / l;
+  const float inv = DROP ? a.drop_inv / l : 1.f / l;
   if (q < a.Nq) {
     T* O = reinterpret_cast<T*>(a.out) + b * a.os[0] + hh * a.os[2] + (long long)q * a.os[1];
 #pragma unroll
@@ -257,7 +278,10 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : ((DP == 64 && sizeof(T) == 2 &
 }
 
 // ===================================================================== backward: dK, dV
-template <typename T, int DP, bool VEC, bool REL>
+// DROP (both backward passes): with m = keep / pk, dV = (P o m)^T dO and dS = P o (m o dP - delta).
+// The dP accumulator then starts from zero (m o (dP - delta) != m o dP - delta) and -delta is
+// added on the VALU.
+template <typename T, int DP, bool VEC, bool REL, bool DROP = false>
 __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dkdv_kernel(AttnArgs a) {
   using M = MF<T>;
   using I = Img<T, DP>;
@@ -297,6 +321,9 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dkdv_kernel(A
   for (int t = 0; t < NT; ++t) { adk[t] = zero16(); adv[t] = zero16(); }
 
   const float sl2 = a.scale * kLog2e;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
   int kx = 0, ky = 0;
   if constexpr (REL) {
     const int kk = min(key, a.Nk - 1);
@@ -374,7 +401,7 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dkdv_kernel(A
 #pragma unroll 1
     for (int u = 0; u < nu; ++u) {
       // row constants as the initial accumulators: S - lse/scale and dP - delta
-      f32x16 sp, dp;
+      f32x16 sp, dp, nd;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 l4 = *reinterpret_cast<const f32x4*>(ldsL + 32 * u + 8 * g + 4 * h);
@@ -382,9 +409,12 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dkdv_kernel(A
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           sp[4 * g + j] = l4[j];
-          dp[4 * g + j] = d4[j];
+          dp[4 * g + j] = DROP ? 0.f : d4[j];
+          nd[4 * g + j] = d4[j];
         }
       }
+      unsigned keep = 0;
+      if constexpr (DROP) keep = drop_keep16<false>(dkey, a.drop_thr, bh, key, (qt * kBQT + 32 * u + 4 * h) >> 2);
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         sp = M::mma(I::rowfrag(ldsQ, 32 * u + r32, s, h), kf[s], sp);
@@ -399,8 +429,14 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dkdv_kernel(A
           x += ldsB[ql * RW + kx] + ldsB[ql * RW + a.rel_h + ky];
         }
         const float p = ex2(x);
-        sp[r] = p;
-        dp[r] = p * dp[r];
+        if constexpr (DROP) {
+          const float pm = ((keep >> r) & 1u) ? p * a.drop_inv : 0.f;
+          sp[r] = pm;
+          dp[r] = __builtin_fmaf(pm, dp[r], p * nd[r]);
+        } else {
+          sp[r] = p;
+          dp[r] = p * dp[r];
+        }
       }
 #pragma unroll
       for (int s2 = 0; s2 < NP; ++s2) {
@@ -446,7 +482,7 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dkdv_kernel(A
 }
 
 // ========================================================================= backward: dQ
-template <typename T, int DP, bool VEC, bool REL>
+template <typename T, int DP, bool VEC, bool REL, bool DROP = false>
 __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dq_kernel(AttnArgs a) {
   using M = MF<T>;
   using I = Img<T, DP>;
@@ -523,6 +559,9 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dq_kernel(Att
   for (int t = 0; t < NT; ++t) adq[t] = zero16();
   const float sl2 = a.scale * kLog2e;
   const int nkt = (a.Nk + kBK - 1) / kBK;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
 
   Stage<T, DP, kBK, VEC> kst, vst;
   const __amdgpu_buffer_rsrc_t rk = row_rsrc(K, a.Nk, a.ks[1]);
@@ -559,8 +598,10 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dq_kernel(Att
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         sp[r] = lsc;
-        dp[r] = -dlt;
+        dp[r] = DROP ? 0.f : -dlt;
       }
+      unsigned keep = 0;
+      if constexpr (DROP) keep = drop_keep16<true>(dkey, a.drop_thr, bh, q, (kt * kBK + 32 * u + 4 * h) >> 2);
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         sp = M::mma(I::rowfrag(ldsK, 32 * u + r32, s, h), qf[s], sp);
@@ -579,7 +620,9 @@ __global__ __launch_bounds__(256, DP >= 128 ? 1 : 2) void attn_bwd_dq_kernel(Att
           x += wb[r32 * RW + kx] + wb[r32 * RW + a.rel_h + ky];
         }
         const float p = (!tail || key < a.Nk) ? ex2(x) : 0.f;
-        const float ds = p * dp[r];
+        float ds;
+        if constexpr (DROP) ds = p * ((((keep >> r) & 1u) ? dp[r] * a.drop_inv : 0.f) - dlt);
+        else ds = p * dp[r];
         dp[r] = ds;
         if constexpr (REL) {
           if (key < a.Nk) {

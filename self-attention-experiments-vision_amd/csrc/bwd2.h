@@ -24,7 +24,10 @@ namespace sae {
 // (fwd2.h rel_onehot8 / rel_qrow8); the dQ pass also forms dbias^T = onehot^T dS^T on the matrix
 // pipe -- one more 32 x 32 accumulator, complete per query row because the pass sweeps every key
 // -- and stores dbias_h / dbias_w (deterministic, no atomics).
-template <int DP, int NW, int MINW, bool ROT = false, bool REL = false>
+// DROP (both passes): dropout on the probabilities (dropout.h): with m = keep / pk,
+// dV = (P o m)^T dO and dS = P o (m o dP - delta).  m o (dP - delta) != m o dP - delta, so the dP
+// accumulator starts from zero and -delta is added on the VALU.
+template <int DP, int NW, int MINW, bool ROT = false, bool REL = false, bool DROP = false>
 __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dq_kernel(AttnArgs a) {
   using FF = F2<DP>;
   constexpr int NS = FF::NS, NT = FF::NT, TILE = FF::TILE;
@@ -89,6 +92,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dq_kernel(AttnArgs a)
   if (qok && h == 0) a.delta[rowoff + q] = dlt;
   const float lsc2 = qok ? -a.lse[rowoff + q] * kLog2e : -kInf;
   const float sl2 = a.scale * kLog2e;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
 
   unsigned ka[NS], ca[2 * NT];
 #pragma unroll
@@ -168,7 +174,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dq_kernel(AttnArgs a)
       for (int u = 0; u < 2; ++u) {
         if (u == 1 && nvalid <= 32) break;
         f32x16 sp = zero16();
-        f32x16 dp = MF<__bf16>::mma(dl_a, dl_b, zero16());
+        f32x16 dp = DROP ? zero16() : MF<__bf16>::mma(dl_a, dl_b, zero16());
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           const bf16x8 kr = *reinterpret_cast<const bf16x8*>(ldsK + ka[s] + 32 * u * DP * 2);
@@ -186,8 +192,15 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dq_kernel(AttnArgs a)
 #pragma unroll
           for (int r = 0; r < 16; ++r) sp[r] = ((r & 3) + 8 * (r >> 2)) < nvh ? sp[r] : -kInf;
         }
+        if constexpr (DROP) {
+          const unsigned keep = drop_keep16<true>(dkey, a.drop_thr, bh, q, 16 * t + 8 * u + h);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dp[r] *= ex2(__builtin_fmaf(sp[r], sl2, lsc2));
+          for (int r = 0; r < 16; ++r)
+            dp[r] = ex2(__builtin_fmaf(sp[r], sl2, lsc2)) * ((((keep >> r) & 1u) ? dp[r] * a.drop_inv : 0.f) - dlt);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dp[r] *= ex2(__builtin_fmaf(sp[r], sl2, lsc2));
+        }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
           const bf16x8 sf = acc_frag<__bf16>(dp, s2);
@@ -259,7 +272,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dq_kernel(AttnArgs a)
 // dV^T += dO^T P and dK^T += Q^T dS (transposed reads of the dO / Q images).
 // REL: the staged tile also carries the query-bias rows of its 64 queries ([64][32] bf16 image),
 // the wave's keys hold their one-hot rows in registers.
-template <int DP, int NW, int MINW, bool ROT = false, bool REL = false>
+template <int DP, int NW, int MINW, bool ROT = false, bool REL = false, bool DROP = false>
 __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dkdv_kernel(AttnArgs a) {
   using FF = F2<DP>;
   constexpr int NS = FF::NS, NT = FF::NT, TILE = FF::TILE;
@@ -347,6 +360,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dkdv_kernel(AttnArgs 
     }
   }
   const float sl2 = a.scale * kLog2e;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
 
   unsigned ra[NS], ca[2 * NT];
 #pragma unroll
@@ -413,7 +429,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dkdv_kernel(AttnArgs 
           }
         }
         f32x16 sp = zero16();
-        f32x16 dp = MF<__bf16>::mma(dla, one01, zero16());
+        f32x16 dp = DROP ? zero16() : MF<__bf16>::mma(dla, one01, zero16());
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           const bf16x8 qr = *reinterpret_cast<const bf16x8*>(ldsQ + ra[s] + 32 * u * DP * 2);
@@ -428,14 +444,24 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_bwd2_dkdv_kernel(AttnArgs 
             sp = MF<__bf16>::mma(*reinterpret_cast<const bf16x8*>(ldsR + rra[s] + 32 * u * 64), kfa[s], sp);
         }
         // rows q = 32u + row_of(r, h): constants for r = 4g + j at 32u + 8g + 4h + j
+        unsigned keep = 0;
+        if constexpr (DROP) keep = drop_keep16<false>(dkey, a.drop_thr, bh, key, 16 * qt + 8 * u + h);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const f32x4 l4 = *reinterpret_cast<const f32x4*>(ldsL + 32 * u + 8 * g + 4 * h);
+          f32x4 d4 = {};
+          if constexpr (DROP) d4 = *reinterpret_cast<const f32x4*>(ldsD + 32 * u + 8 * g + 4 * h);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float p = ex2(__builtin_fmaf(sp[4 * g + j], sl2, -l4[j]));
-            sp[4 * g + j] = p;
-            dp[4 * g + j] *= p;
+            if constexpr (DROP) {
+              const float pm = ((keep >> (4 * g + j)) & 1u) ? p * a.drop_inv : 0.f;
+              sp[4 * g + j] = pm;
+              dp[4 * g + j] = __builtin_fmaf(pm, dp[4 * g + j], -(p * d4[j]));
+            } else {
+              sp[4 * g + j] = p;
+              dp[4 * g + j] *= p;
+            }
           }
         }
 #pragma unroll

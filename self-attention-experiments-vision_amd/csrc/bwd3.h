@@ -126,7 +126,9 @@ template <int DP, int NW> struct B3Stage {
 // one of waves 0-3) runs the previous tile's dQ product at the START of a step instead of at its
 // end, so the two waves of a SIMD are in different phases of the step (one's exponentials beside the
 // other's MFMAs) instead of in lockstep (MI355X_MICROARCH.md, two waves per SIMD, item 9)
-template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16>
+// DROP: dropout on the probabilities (dropout.h), the algebra of bwd2.h: the dP accumulator starts
+// from zero and -delta is added on the VALU.
+template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16, bool DROP = false>
 __global__ __launch_bounds__(64 * NW, (NW * KPW == 8 && KPW == 1) ? 2 : 1) void attn_bwd3_kernel(AttnArgs a) {
   using C = B3<DP, NW, KPW>;
   constexpr int NS = NSU, NT = C::NT, TB = C::TB, KS = C::KS;
@@ -254,6 +256,9 @@ __global__ __launch_bounds__(64 * NW, (NW * KPW == 8 && KPW == 1) ? 2 : 1) void 
 #pragma unroll
   for (int j = 0; j < 8; ++j) one01[j] = (__bf16)((h == 0 && j < 2) ? 1.f : 0.f);
   const float sl2 = a.scale * kLog2e;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
   __syncthreads();   // every wave holds its K^T fragments: the K image becomes the dS images
   SAE_STAMP(2);
   if (!active) {     // a wave past the last key writes zero dS once (its K rows are zero)
@@ -310,17 +315,25 @@ __global__ __launch_bounds__(64 * NW, (NW * KPW == 8 && KPW == 1) ? 2 : 1) void 
     const bool late = w >= NW / 2;   // this wave runs the previous tile's dQ first
     if (late && qt > 0) dq_tile(dsb + (bsel ^ 1) * C::DSIMG, qt - 1);
     if (active) {
+      // DROP: the tile's keep bits first, while no operand of the tile is live
+      unsigned keep[KPW] = {};
+      if constexpr (DROP) {
+#pragma unroll
+        for (int j = 0; j < KPW; ++j) keep[j] = drop_keep16<false>(dkey, a.drop_thr, bh, wrow + 32 * j + r32, 8 * qt + h);
+      }
       bf16x8 qr[NS], gr[NS];
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         qr[s] = *reinterpret_cast<const bf16x8*>(ldsQ + ra[s]);
         gr[s] = *reinterpret_cast<const bf16x8*>(ldsG + ra[s]);
       }
-      f32x4 l4[4];
+      f32x4 l4[4];   // (DROP: read with -delta after the products instead, 16 registers fewer across them)
+      if constexpr (!DROP) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) l4[g] = *reinterpret_cast<const f32x4*>(ldsL + 8 * g + 4 * h);
+        for (int g = 0; g < 4; ++g) l4[g] = *reinterpret_cast<const f32x4*>(ldsL + 8 * g + 4 * h);
+      }
       bf16x8 dla;
-      {
+      if constexpr (!DROP) {
         const float nd = ldsD[r32];
         const __bf16 hi = (__bf16)nd;
         const __bf16 lo = (__bf16)(nd - (float)hi);
@@ -335,7 +348,7 @@ __global__ __launch_bounds__(64 * NW, (NW * KPW == 8 && KPW == 1) ? 2 : 1) void 
 #pragma unroll
       for (int j = 0; j < KPW; ++j) {
         sp[j] = zero16();
-        dp[j] = MF<__bf16>::mma(dla, one01, zero16());
+        dp[j] = DROP ? zero16() : MF<__bf16>::mma(dla, one01, zero16());
       }
 #pragma unroll
       for (int s = 0; s < NS; ++s)
@@ -347,15 +360,28 @@ __global__ __launch_bounds__(64 * NW, (NW * KPW == 8 && KPW == 1) ? 2 : 1) void 
       // rows q = row_of(r, h): constants for r = 4g + i at 8g + 4h + i.  P <= 1 always (lse bounds
       // every score of the row); the clamp keeps keys past Nk (zero K rows) finite.
 #pragma unroll
-      for (int j = 0; j < KPW; ++j)
+      for (int j = 0; j < KPW; ++j) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
+        for (int g = 0; g < 4; ++g) {
+          f32x4 nd4 = {};
+          if constexpr (DROP) {
+            nd4 = *reinterpret_cast<const f32x4*>(ldsD + 8 * g + 4 * h);
+            l4[g] = *reinterpret_cast<const f32x4*>(ldsL + 8 * g + 4 * h);
+          }
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float p = __builtin_amdgcn_fmed3f(ex2(__builtin_fmaf(sp[j][4 * g + i], sl2, -l4[g][i])), 0.f, 1.f);
-            sp[j][4 * g + i] = p;
-            dp[j][4 * g + i] *= p;
+            if constexpr (DROP) {
+              const float pm = ((keep[j] >> (4 * g + i)) & 1u) ? p * a.drop_inv : 0.f;
+              sp[j][4 * g + i] = pm;
+              dp[j][4 * g + i] = __builtin_fmaf(pm, dp[j][4 * g + i], p * nd4[i]);
+            } else {
+              sp[j][4 * g + i] = p;
+              dp[j][4 * g + i] *= p;
+            }
           }
+        }
+      }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const int ro_ = 16 * s2 * DP * 2;

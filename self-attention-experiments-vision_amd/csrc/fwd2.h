@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dropout.h"
 
 namespace sae {
 
@@ -146,15 +147,28 @@ struct F2Stage {
 // row's sum left [1, 2^64) (a later tile's score more than 64 log2 units above the first tile's
 // max).  P is fed to the MFMA in bf16, whose relative precision does not depend on magnitude,
 // so the result is that of the tracking sweep up to fp32 summation order.
-template <int DP, int NW, bool LSUM, bool FIRST, int NSU = F2<DP>::NS, bool REL = false, bool FIX = false>
+// DROP: attention-probability dropout (dropout.h): the dropped P are zeroed after the exponent and
+// the row sum, before they feed the AV product, so l and the FIX range check see the undropped P
+// -- which is why the dropout instances take the VALU row sum (the all-ones MFMA row sum reads the
+// fragment that feeds AV).  kb4 = (first key of the tile + 4h) / 4.
+template <int DP, int NW, bool LSUM, bool FIRST, int NSU = F2<DP>::NS, bool REL = false, bool FIX = false,
+          bool DROP = false>
 __device__ __forceinline__ void fwd2_tile(const char* ldsK, const char* ldsV, const bf16x8* qf, f32x16* acco,
                                           f32x16& lacc, float& m, float& l, int nvalid, float sl2,
                                           const unsigned* ka, const unsigned* va, int h,
                                           const char* ldsR = nullptr, const unsigned* ra = nullptr,
-                                          const bf16x8* qa = nullptr) {
+                                          const bf16x8* qa = nullptr, const DropKey* dk = nullptr,
+                                          unsigned thr = 0, unsigned bh = 0, int q = 0, int kb4 = 0) {
+  static_assert(!DROP || !LSUM, "the dropout instances sum the undropped P on the VALU");
   constexpr int NS = NSU, NT = F2<DP>::NT;
   // nvalid: keys of this tile that exist (64 for every tile but the tail)
   const bool two = nvalid > 32;
+  // DROP: the tile's keep bits first, while no score is live (two registers from here on)
+  unsigned keep0 = 0, keep1 = 0;
+  if constexpr (DROP) {
+    keep0 = drop_keep16<true>(*dk, thr, bh, q, kb4);
+    if (two) keep1 = drop_keep16<true>(*dk, thr, bh, q, kb4 + 8);
+  }
   f32x16 s0 = zero16(), s1 = zero16();
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
@@ -226,6 +240,14 @@ __device__ __forceinline__ void fwd2_tile(const char* ldsK, const char* ldsV, co
     if (two) ls += f2_tree16(s1);
     l = FIRST ? ls : l + ls;
   }
+  if constexpr (DROP) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s0[r] = ((keep0 >> r) & 1u) ? s0[r] : 0.f;
+    if (two) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s1[r] = ((keep1 >> r) & 1u) ? s1[r] : 0.f;
+    }
+  }
   bf16x8 ones;
 #pragma unroll
   for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.f;
@@ -268,8 +290,9 @@ __device__ __forceinline__ void fwd2_tile(const char* ldsK, const char* ldsV, co
 // K tile as it goes to LDS -- so the rotated tensors never exist in HBM.
 // REL: BoTNet relative logits as two extra score k-steps (rel_onehot8 / rel_qrow8 above); the
 // one-hot images follow the K / V buffers in LDS.
+// DROP: dropout on the probabilities (fwd2_tile); 1 / pk is folded into the final 1 / l.
 template <int DP, int NW, int MINW, bool LSUM, bool ROT = false, int NSU = DP / 16, bool REL = false,
-          bool FIX = false>
+          bool FIX = false, bool DROP = false>
 __global__ __launch_bounds__(64 * NW, MINW) void attn_fwd2_kernel(AttnArgs a) {
   using FF = F2<DP>;
   constexpr int NS = NSU, NT = FF::NT, TILE = FF::TILE;
@@ -349,6 +372,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fwd2_kernel(AttnArgs a) {
   f32x16 acco[NT], lacc;   // written first by the peeled first tile (zero C operand)
   float m = -kInf, l = 0.f;
   const float sl2 = a.scale * kLog2e;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_rng, a.drop_stream);
+  const unsigned bh = (unsigned)(b * a.H + hh);
 
   if constexpr (ROT) kst.rope(a.rope, 0, tid);
   kst.write(smem);
@@ -369,9 +395,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fwd2_kernel(AttnArgs a) {
       vst.load(rv, (unsigned)(t + 1) * vstep);
     }
     if constexpr (decltype(compute_c)::value) {
-      fwd2_tile<DP, NW, LSUM, decltype(first_c)::value, NSU, REL, decltype(fix_c)::value>(
+      fwd2_tile<DP, NW, LSUM, decltype(first_c)::value, NSU, REL, decltype(fix_c)::value, DROP>(
           cur, cur + TILE, qf, acco, lacc, m, l, min(64, a.Nk - 64 * t), sl2, ka, va, h, rimg + bsel * kRelImg, ra,
-          qa);
+          qa, &dkey, a.drop_thr, bh, q, 16 * t + h);
     }
     if (t + 1 < nkt) {
       if constexpr (ROT) kst.rope(a.rope, 64 * (t + 1), tid);
@@ -415,7 +441,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fwd2_kernel(AttnArgs a) {
   float lt;
   if constexpr (LSUM) lt = lacc[0];
   else lt = xhalf_sum(l);
-  const float inv = 1.f / lt;
+  const float inv = DROP ? a.drop_inv / lt : 1.f / lt;
   {  // O rows through a per-wave LDS scratch (the K/V images are free after the last barrier)
     const int q0 = qb * BQ + w * 32;
     __bf16* O = reinterpret_cast<__bf16*>(a.out) + b * a.os[0] + hh * a.os[2] + (long long)q0 * a.os[1];

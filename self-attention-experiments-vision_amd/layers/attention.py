@@ -141,10 +141,14 @@ class AttentionBlock(nn.Module):
             self._build(in_ch, inputs_q.device)
         elif self._in_ch != in_ch:
             raise ValueError(f"AttentionBlock built for {self._in_ch} channels, got {in_ch}")
+        # attention-probability dropout (attention.py:54-58): inside the attention kernels
+        drop = None
         if is_training and self.attn_dropout_rate > 0.0:
-            raise NotImplementedError(
-                "attention-probability dropout (attn_dropout_rate > 0 while training) is not fused into the "
-                "HIP kernel; every reference config uses rate 0 (vit.py:68, create_model.py)")
+            if self.talking_heads:
+                raise NotImplementedError(
+                    "attn_dropout_rate > 0 with talking_heads=True is not implemented: the reference drops after "
+                    "the second head mix (attention.py:50-56), and the talking-heads kernels have no dropout")
+            drop = (self.attn_dropout_rate, ops.dropout_rng(inputs_q.device))
         H, D = self.num_heads, self._head_ch_eff
         dt = self.dtype
         B, Nq, C = inputs_q.shape
@@ -177,9 +181,9 @@ class AttentionBlock(nn.Module):
             o = ops.talking_heads_attention(q, k, v, self.TalkingHeadsBlock_0.talking_heads_transform,
                                             self.TalkingHeadsBlock_1.talking_heads_transform, scale, rope)
         elif self_attn:
-            o = ops.attention_packed(qkv, scale, rope)
+            o = ops.attention_packed(qkv, scale, rope, dropout=drop)
         else:
-            o = ops.attention(q, k, v, scale, rotary=rope)
+            o = ops.attention(q, k, v, scale, rotary=rope, dropout=drop)
         wo = self.DenseGeneral_0.kernel.reshape(HD, self._out_ch_eff)
         y = ops.dense(o.reshape(B, Nq, HD), wo, self.DenseGeneral_0.bias if self.use_bias else None, dt)
         if self.out_dropout_rate > 0.0:

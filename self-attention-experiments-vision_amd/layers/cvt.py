@@ -137,9 +137,13 @@ class CvTAttentionBlock(nn.Module):
         assert in_ch % self.num_heads == 0
         if self._in_ch is None:
             self._build(in_ch, inputs_q.device)
+        drop = None   # attention-probability dropout (cvt_attention.py:100-104): inside the kernels
         if is_training and self.attn_dropout_rate > 0.0:
-            raise NotImplementedError("attention-probability dropout is not fused into the HIP kernel "
-                                      "(no reference config sets attn_dropout_rate)")
+            if self.talking_heads:
+                raise NotImplementedError(
+                    "attn_dropout_rate > 0 with talking_heads=True is not implemented: the reference drops after "
+                    "the second head mix, and the talking-heads kernels have no dropout")
+            drop = (self.attn_dropout_rate, ops.dropout_rng(inputs_q.device))
         H, D, dt = self.num_heads, self._D, self.dtype
         q = self.ConvProjectionBlock_0(inputs_q, is_training)
         k = self.ConvProjectionBlock_1(inputs_kv, is_training)
@@ -151,7 +155,7 @@ class CvTAttentionBlock(nn.Module):
             o = ops.talking_heads_attention(q, k, v, self.TalkingHeadsBlock_0.talking_heads_transform,
                                             self.TalkingHeadsBlock_1.talking_heads_transform, scale)
         else:
-            o = ops.attention(q, k, v, scale)
+            o = ops.attention(q, k, v, scale, dropout=drop)
         y = ops.dense(o.reshape(b, -1, H * D), self.DenseGeneral_0.kernel.reshape(H * D, self._out),
                       self.DenseGeneral_0.bias if self.use_bias else None, dt)
         if self.out_dropout_rate > 0.0:

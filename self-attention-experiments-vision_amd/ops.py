@@ -185,7 +185,84 @@ def rope_fused_ok(*ts: torch.Tensor) -> bool:
                 and t.data_ptr() % 16 == 0 for t in ts))
 
 
-def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None):
+# ------------------------------------------------------------------- attention dropout state
+class DropoutRng:
+    """Device state of the attention-probability dropout (``sae_attn_fwd_dropout``): a 2-element
+    int64 tensor carrying the bit patterns of ``{seed, offset}``.  The kernels read it on the
+    device, so a captured step replays with fresh masks once :meth:`advance` has run on the stream.
+    Every attention call of a step draws its own ``stream_id`` from :meth:`next_stream` (a host
+    counter since the last advance); the backward of a call passes the id its forward drew."""
+
+    def __init__(self, seed: int, device):
+        self.device = torch.device(device)
+        self.state = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.seed(seed)
+
+    def seed(self, seed: int, offset: int = 0) -> None:
+        """Set ``{seed, offset}`` (64-bit patterns) and restart the call counter."""
+        def i64(x):
+            x = int(x) & 0xFFFFFFFFFFFFFFFF
+            return x - (1 << 64) if x >= (1 << 63) else x
+        self.state.copy_(torch.tensor([i64(seed), i64(offset)], dtype=torch.int64))
+        self._calls = 0
+
+    def next_stream(self) -> int:
+        sid = self._calls
+        self._calls += 1
+        return sid
+
+    def advance(self, n: int = 1) -> None:
+        """``offset += n`` on the current stream (``sae_dropout_advance``); restarts the call counter."""
+        lib = L.load()
+        _require_gpu(self.state)
+        L.check(lib.sae_dropout_advance(_stream(self.state), _ptr(self.state), int(n)))
+        self._calls = 0
+
+
+_DROPOUT_RNGS = {}
+
+
+def dropout_rng(device) -> DropoutRng:
+    """The default :class:`DropoutRng` of ``device`` (seed 0 until :func:`seed_dropout`)."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    r = _DROPOUT_RNGS.get(dev)
+    if r is None:
+        r = _DROPOUT_RNGS[dev] = DropoutRng(0, dev)
+    return r
+
+
+def seed_dropout(seed: int) -> None:
+    """Seed the default dropout state of every device that has one, and of the current device."""
+    if torch.cuda.is_available():
+        dropout_rng("cuda")
+    for r in _DROPOUT_RNGS.values():
+        r.seed(seed)
+
+
+def dropout_mask(B: int, H: int, Nq: int, Nk: int, rate: float, rng: DropoutRng, stream_id: int) -> torch.Tensor:
+    """uint8 ``keep[B, H, Nq, Nk]`` exactly as the dropout attention kernels apply it
+    (``sae_attn_dropout_mask``)."""
+    lib = L.load()
+    _require_gpu(rng.state)
+    keep = torch.empty((B, H, Nq, Nk), dtype=torch.uint8, device=rng.state.device)
+    L.check(lib.sae_attn_dropout_mask(_stream(keep), B, H, Nq, Nk, float(rate), _ptr(rng.state), int(stream_id),
+                                      _ptr(keep)))
+    return keep
+
+
+def _draw(dropout):
+    """``(rate, rng)`` of the public ops -> ``(rate, state tensor, stream_id)`` of one call."""
+    if dropout is None:
+        return None
+    rate, rng = dropout
+    if not 0.0 <= float(rate) < 1.0:
+        raise ValueError(f"dropout rate {rate} is outside [0, 1)")
+    return (float(rate), rng.state, rng.next_stream())
+
+
+def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None, drop=None):
     lib = L.load()
     B, Nq, H, D = q.shape
     o = torch.empty((B, Nq, H, D), dtype=q.dtype, device=q.device)
@@ -196,6 +273,9 @@ def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None):
         sin, cos = _rope_tabs(q, k, rope)
         L.check(lib.sae_attn_fwd_rotary(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(sin),
                                         _ptr(cos), _ptr(o), _ptr(lse)))
+    elif drop is not None:
+        L.check(lib.sae_attn_fwd_dropout(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
+                                         drop[0], _ptr(drop[1]), drop[2]))
     else:
         L.check(lib.sae_attn_fwd(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(bias_h),
                                  _ptr(bias_w), _ptr(o), _ptr(lse)))
@@ -204,7 +284,7 @@ def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None):
     return o, lse
 
 
-def _bwd(q, k, v, o, lse, do, dq, dk, dv, scale, bias_h=None, bias_w=None, grid=None, rope=None):
+def _bwd(q, k, v, o, lse, do, dq, dk, dv, scale, bias_h=None, bias_w=None, grid=None, rope=None, drop=None):
     lib = L.load()
     d = _make_desc(q, k, v, o, scale, do, dq, dk, dv, grid=grid)
     ws = torch.empty(lib.sae_attn_bwd_workspace_bytes(ctypes.byref(d)), dtype=torch.uint8, device=q.device)
@@ -216,6 +296,10 @@ def _bwd(q, k, v, o, lse, do, dq, dk, dv, scale, bias_h=None, bias_w=None, grid=
         sin, cos = _rope_tabs(q, k, rope)
         L.check(lib.sae_attn_bwd_rotary(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
                                         _ptr(do), _ptr(sin), _ptr(cos), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws)))
+    elif drop is not None:
+        L.check(lib.sae_attn_bwd_dropout(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
+                                         _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), drop[0], _ptr(drop[1]),
+                                         drop[2]))
     else:
         L.check(lib.sae_attn_bwd(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
                                  _ptr(do), _ptr(bias_h), _ptr(bias_w), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dbh),
@@ -231,11 +315,11 @@ def _grad_in(g: torch.Tensor) -> torch.Tensor:
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, bias_h, bias_w, grid, rope):
+    def forward(ctx, q, k, v, scale, bias_h, bias_w, grid, rope, drop):
         _require_gpu(q, k, v)
-        o, lse = _fwd(q, k, v, scale, bias_h, bias_w, grid, rope)
+        o, lse = _fwd(q, k, v, scale, bias_h, bias_w, grid, rope, drop)
         ctx.save_for_backward(q, k, v, o, lse, bias_h, bias_w)
-        ctx.scale, ctx.grid, ctx.rope = scale, grid, rope
+        ctx.scale, ctx.grid, ctx.rope, ctx.drop = scale, grid, rope, drop
         return o
 
     @staticmethod
@@ -246,18 +330,18 @@ class _Attention(torch.autograd.Function):
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         dk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
         dv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        dbh, dbw = _bwd(q, k, v, o, lse, do, dq, dk, dv, ctx.scale, bias_h, bias_w, ctx.grid, ctx.rope)
-        return dq, dk, dv, None, dbh, dbw, None, None
+        dbh, dbw = _bwd(q, k, v, o, lse, do, dq, dk, dv, ctx.scale, bias_h, bias_w, ctx.grid, ctx.rope, ctx.drop)
+        return dq, dk, dv, None, dbh, dbw, None, None, None
 
 
 class _AttentionPacked(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, scale, rope):
+    def forward(ctx, qkv, scale, rope, drop):
         _require_gpu(qkv)
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
-        o, lse = _fwd(q, k, v, scale, rope=rope)
+        o, lse = _fwd(q, k, v, scale, rope=rope, drop=drop)
         ctx.save_for_backward(qkv, o, lse)
-        ctx.scale, ctx.rope = scale, rope
+        ctx.scale, ctx.rope, ctx.drop = scale, rope, drop
         return o
 
     @staticmethod
@@ -267,43 +351,55 @@ class _AttentionPacked(torch.autograd.Function):
         do = _grad_in(do)
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
         _bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2],
-             ctx.scale, rope=ctx.rope)
-        return dqkv, None, None
+             ctx.scale, rope=ctx.rope, drop=ctx.drop)
+        return dqkv, None, None, None
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
               bias: Optional[Tuple[torch.Tensor, torch.Tensor, Tuple[int, int]]] = None,
-              rotary: Optional[float] = None) -> torch.Tensor:
+              rotary: Optional[float] = None, dropout=None) -> torch.Tensor:
     """softmax(scale * q k^T [+ relpos bias]) v on token-major [B, N, H, D] tensors.
 
     ``scale`` defaults to the reference's 1/sqrt(head_ch) (attention.py:39).  ``bias`` is
     ``(bias_h, bias_w, (Hs, Ws))`` from :func:`relpos_bias` (BoTNet).  ``rotary`` (a base, e.g.
     10000.0): q and k are rotated first (position_embed.py:8-20) -- inside the kernels' staging
-    where they take it (:func:`rope_fused_ok`), else by the standalone rotary pass."""
+    where they take it (:func:`rope_fused_ok`), else by the standalone rotary pass.  ``dropout`` is
+    ``(rate, DropoutRng)``: the probabilities are dropped inside the kernels (attention.py:54-58;
+    the rate is quantised to n / 256, below 1 / 512 nothing is dropped); rotary then runs as the
+    standalone pass, and relative logits are not supported with it."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if dropout is not None:
+        if bias is not None:
+            raise NotImplementedError("attention dropout with relative logits is not implemented")
+        if rotary is not None:
+            q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))
+        return _Attention.apply(q, k, v, float(scale), None, None, None, None, _draw(dropout))
     if rotary is not None and bias is None:
         if rope_fused_ok(q, k, v):
-            return _Attention.apply(q, k, v, float(scale), None, None, None, float(rotary))
+            return _Attention.apply(q, k, v, float(scale), None, None, None, float(rotary), None)
         q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))
     elif rotary is not None:
         q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))
     if bias is None:
-        return _Attention.apply(q, k, v, float(scale), None, None, None, None)
+        return _Attention.apply(q, k, v, float(scale), None, None, None, None, None)
     bh, bw, grid = bias
-    return _Attention.apply(q, k, v, float(scale), bh, bw, tuple(grid), None)
+    return _Attention.apply(q, k, v, float(scale), bh, bw, tuple(grid), None, None)
 
 
-def attention_packed(qkv: torch.Tensor, scale: Optional[float] = None, rotary: Optional[float] = None) -> torch.Tensor:
+def attention_packed(qkv: torch.Tensor, scale: Optional[float] = None, rotary: Optional[float] = None,
+                     dropout=None) -> torch.Tensor:
     """Self-attention on a packed projection ``qkv`` [B, N, 3, H, D] (one fused QKV GEMM output);
-    ``rotary`` as in :func:`attention`."""
+    ``rotary`` and ``dropout`` as in :func:`attention`."""
     if qkv.dim() != 5 or qkv.shape[2] != 3:
         raise ValueError(f"expected qkv [B, N, 3, H, D], got {tuple(qkv.shape)}")
     if scale is None:
         scale = 1.0 / math.sqrt(qkv.shape[-1])
-    if rotary is not None and not rope_fused_ok(qkv[:, :, 0]):
-        return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale, rotary=rotary)
-    return _AttentionPacked.apply(qkv, float(scale), None if rotary is None else float(rotary))
+    if rotary is not None and (dropout is not None or not rope_fused_ok(qkv[:, :, 0])):
+        return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale, rotary=rotary, dropout=dropout)
+    if dropout is not None:
+        return _AttentionPacked.apply(qkv, float(scale), None, _draw(dropout))
+    return _AttentionPacked.apply(qkv, float(scale), None if rotary is None else float(rotary), None)
 
 
 # ----------------------------------------------------------------------------- talking heads

@@ -395,6 +395,14 @@ class TrainStep:
             except (RuntimeError, TypeError):
                 self.opt = torch.optim.AdamW(params, foreach=True, **kw)
         self.smoothing = label_smoothing
+        # attention-probability dropout (attn_dropout_rate > 0 on any module): the first operation
+        # of each step bumps the device offset of the dropout state (ops.DropoutRng.advance), so
+        # every step -- every replay of the captured graph included -- draws fresh masks.  With
+        # rate 0 everywhere the step launches nothing for it.
+        self._drop_rng = None
+        if on_gpu and any(getattr(m, "attn_dropout_rate", 0.0) > 0.0 for m in model.modules()):
+            from . import ops
+            self._drop_rng = ops.dropout_rng(params[0].device)
 
     @staticmethod
     def _broadcast_from_rank0(tensors):
@@ -525,6 +533,8 @@ class TrainStep:
 
     def _fwd_bwd(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         from . import ops
+        if self._drop_rng is not None:
+            self._drop_rng.advance()
         self._zero_grad()
         sinks = self.flat and self._sinks
         overlap = self.collective == "overlap"
@@ -610,6 +620,7 @@ class TrainStep:
         had_state = set() if fused else {id(p) for p in params if p in self.opt.state and self.opt.state[p]}
         snap_state = {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.opt.state[p].items()}
                       for p in params if id(p) in had_state}
+        snap_rng = self._drop_rng.state.clone() if self._drop_rng is not None else None
         s = torch.cuda.Stream(device=images.device)
         s.wait_stream(torch.cuda.current_stream(images.device))
         # warm-up on a side stream (allocator, library and optimizer state), collectives off: the
@@ -628,6 +639,8 @@ class TrainStep:
         with torch.no_grad():
             for p, v in zip(params, snap):
                 p.copy_(v)
+            if snap_rng is not None:   # the warm-up steps advanced the dropout offset
+                self._drop_rng.state.copy_(snap_rng)
             if fused:
                 for t, v in zip(self.opt.state_tensors(), snap_fused):
                     t.copy_(v)

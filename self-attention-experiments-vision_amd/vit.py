@@ -77,11 +77,12 @@ class FFBlock(nn.Module):
 class EncoderBlock(nn.Module):
     """vit.py:9-32."""
 
-    def __init__(self, dim, num_heads, expand_ratio, dtype, device=None):
+    def __init__(self, dim, num_heads, expand_ratio, dtype, device=None, attn_dropout_rate: float = 0.0):
         super().__init__()
         self.dtype = dtype
         self.LayerNorm_0 = LayerNorm(dim, device)
-        self.SelfAttentionBlock_0 = SelfAttentionBlock(num_heads=num_heads, dtype=dtype, in_ch=dim, device=device)
+        self.SelfAttentionBlock_0 = SelfAttentionBlock(num_heads=num_heads, attn_dropout_rate=attn_dropout_rate,
+                                                       dtype=dtype, in_ch=dim, device=device)
         self.LayerNorm_1 = LayerNorm(dim, device)
         self.FFBlock_0 = FFBlock(dim, expand_ratio, device)
 
@@ -105,13 +106,15 @@ def encoder_weight_groups(blocks):
 class Encoder(nn.Module):
     """vit.py:35-58 (AddAbsPosEmbed_0 + EncoderBlock_i + LayerNorm_0)."""
 
-    def __init__(self, num_tokens, dim, num_layers, num_heads, expand_ratio, dtype, device=None):
+    def __init__(self, num_tokens, dim, num_layers, num_heads, expand_ratio, dtype, device=None,
+                 attn_dropout_rate: float = 0.0):
         super().__init__()
         self.dtype = dtype
         self.AddAbsPosEmbed_0 = nn.Module()
         self.AddAbsPosEmbed_0.pos_embed = nn.Parameter(torch.randn(1, num_tokens, dim, device=device) * 0.02)
         for i in range(num_layers):
-            setattr(self, f"EncoderBlock_{i}", EncoderBlock(dim, num_heads, expand_ratio, dtype, device))
+            setattr(self, f"EncoderBlock_{i}", EncoderBlock(dim, num_heads, expand_ratio, dtype, device,
+                                                            attn_dropout_rate))
         self.num_layers = num_layers
         self.LayerNorm_0 = LayerNorm(dim, device)
 
@@ -172,7 +175,7 @@ class ViT(nn.Module):
 
     def __init__(self, num_classes: int, num_layers: int, num_heads: int, embed_dim: int,
                  patch_shape: Tuple[int, int], img_size: int = 224, expand_ratio: float = 4,
-                 dtype: torch.dtype = torch.float32, device=None):
+                 dtype: torch.dtype = torch.float32, device=None, attn_dropout_rate: float = 0.0):
         super().__init__()
         assert embed_dim % num_heads == 0
         self.patch_shape, self.dtype, self.embed_dim = tuple(patch_shape), dtype, embed_dim
@@ -181,7 +184,7 @@ class ViT(nn.Module):
         self.PatchEmbedBlock_0.Dense_0 = Dense(ph * pw * 3, embed_dim, use_bias=False, device=device)
         self.cls = nn.Parameter(torch.zeros(1, 1, embed_dim, device=device))
         n = (img_size // ph) * (img_size // pw) + 1
-        self.Encoder_0 = Encoder(n, embed_dim, num_layers, num_heads, expand_ratio, dtype, device)
+        self.Encoder_0 = Encoder(n, embed_dim, num_layers, num_heads, expand_ratio, dtype, device, attn_dropout_rate)
         self.Dense_0 = Dense(embed_dim, num_classes, zero_init=True, device=device)
 
     def cast_groups(self):
@@ -220,13 +223,13 @@ MODEL_CONFIGS = {
 
 
 def create_model(model_name: str, num_classes: int = 1000, dtype: torch.dtype = torch.float32,
-                 img_size: int = 224, device=None) -> ViT:
+                 img_size: int = 224, device=None, attn_dropout_rate: float = 0.0) -> ViT:
     """``create_model`` (models/create_model.py:6-215) for the ViT/DeiT family."""
     if model_name not in MODEL_CONFIGS:
         raise ValueError(f"unknown model {model_name!r}; ViT/DeiT family: {sorted(MODEL_CONFIGS)}")
     L, Hh, C, p = MODEL_CONFIGS[model_name]
     return ViT(num_classes=num_classes, num_layers=L, num_heads=Hh, embed_dim=C, patch_shape=(p, p),
-               img_size=img_size, dtype=dtype, device=device)
+               img_size=img_size, dtype=dtype, device=device, attn_dropout_rate=attn_dropout_rate)
 
 
 def vit_flops_per_image(model_name: str, img_size: int = 224, num_classes: int = 1000) -> float:

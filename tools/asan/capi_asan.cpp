@@ -163,6 +163,17 @@ static void validation() {
   sae_attn_desc_init(&d, 1, 1, 16, 16, 64, SAE_DTYPE_BF16, 0.125f);
   const int rc = sae_attn_fwd(nullptr, &d, q, k, v, nullptr, nullptr, o, lse);
   expect(rc == SAE_OK || rc == SAE_EHIP, "valid launch without a GPU: SAE_EHIP");
+  // dropout entry points: rate, rng and flags are refused on the host
+  const uint64_t* rng = static_cast<const uint64_t*>(fake());
+  expect(sae_attn_fwd_dropout(nullptr, &d, q, k, v, o, lse, 1.0f, rng, 0) == SAE_EINVAL, "dropout rate 1");
+  expect(sae_attn_fwd_dropout(nullptr, &d, q, k, v, o, lse, 0.1f, nullptr, 0) == SAE_EINVAL, "dropout null rng");
+  expect(sae_attn_bwd_dropout(nullptr, &d, q, k, v, o, lse, o, q, k, v, fake(), -0.1f, rng, 0) == SAE_EINVAL,
+         "dropout rate < 0");
+  d.flags = SAE_FLAG_RELPOS;
+  expect(sae_attn_fwd_dropout(nullptr, &d, q, k, v, o, lse, 0.1f, rng, 0) == SAE_EUNSUPPORTED, "dropout + relpos");
+  expect(sae_attn_dropout_mask(nullptr, 1, 1, 4, 4, 0.5f, nullptr, 0, static_cast<uint8_t*>(fake())) == SAE_EINVAL,
+         "mask null rng");
+  expect(sae_dropout_advance(nullptr, nullptr, 1) == SAE_EINVAL, "advance null rng");
 
   expect(sae_gemm_nt(nullptr, 128, 128, 60, q, 64, k, 64, nullptr, o, 128, SAE_EPI_NONE, nullptr, 0, nullptr) ==
              SAE_EUNSUPPORTED,

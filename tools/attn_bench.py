@@ -2,6 +2,7 @@
 """Microbenchmark of the fused attention kernels (fwd, bwd) at the BASELINE shapes.
 
     python tools/attn_bench.py [--iters 50] [--shapes deit_s,vitb384,...] [--dtype bf16]
+    python tools/attn_bench.py --dropout 0.1 --shapes deit_s,vitb384     # rate 0.1 against rate 0
 
 Times each C-ABI call inside HIP graphs of 10 back-to-back launches (HIP events around the
 replay, median over iterations, per-launch time = replay time / 10) and
@@ -43,6 +44,9 @@ def main():
     ap.add_argument("--rope", action="store_true", help="fused rotary (base 10000) on q / k (--th)")
     ap.add_argument("--rel", action="store_true",
                     help="BoTNet relative logits (square Hs = Ws = sqrt(Nk) grid, N(0, 1/D) bias tables)")
+    ap.add_argument("--dropout", type=float, default=None, metavar="RATE",
+                    help="attention-probability dropout: the shapes through sae_attn_*_dropout at RATE and at "
+                         "rate 0, both in this process with their replays alternating; prints both and the ratio")
     ap.add_argument("--fwd-variants", default="", help="comma list of SAE_FWD_VARIANT values to A/B: 0 = default, 1 = v1 kernels (dev build: SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so)")
     ap.add_argument("--bwd-variants", default="", help="comma list of SAE_BWD_VARIANT values to A/B: 0 = default, 1 = v1 kernels, 2 = two-pass bwd2 at Nk <= 256")
     ap.add_argument("--knob", default="", help="NAME=v1,v2,...: any dev-library knob to A/B (dev build)")
@@ -59,6 +63,10 @@ def main():
     kname, kvals = (args.knob.split("=") + [""])[:2] if args.knob else ("", "")
     kv = kvals.split(",") if kname else [""]
     runs = [(n, f, b, x) for n in args.shapes.split(",") for f in fv for b in bv for x in kv]
+    if args.dropout is not None:
+        assert not (args.th or args.rel or args.rope), "--dropout: the plain attention entry points only"
+        dropout_ab(args, runs, dev, dt, results)
+        runs = []
     for shape, fvar, bvar, kval in runs:
         os.environ["SAE_FWD_VARIANT"], os.environ["SAE_BWD_VARIANT"] = fvar, bvar
         if kname:
@@ -141,6 +149,68 @@ def main():
     if args.json:
         with open(args.json, "w") as f:
             json.dump(results, f, indent=1)
+
+
+def dropout_ab(args, runs, dev, dt, results):
+    """--dropout RATE: each shape through the dropout entry points at RATE and at rate 0 (which the
+    library forwards to the plain entry points): graphs of 10 launches as in main(), the replays of
+    the two rates alternating inside every iteration, medians per rate and their ratio."""
+    import torch
+    import sae_vision_amd.ops as ops
+    rng = ops.DropoutRng(1234, dev)
+    reps = 10
+    for shape, fvar, bvar, kval in runs:
+        os.environ["SAE_FWD_VARIANT"], os.environ["SAE_BWD_VARIANT"] = fvar, bvar
+        B, Nq, Nk, H, D = SHAPES[shape]
+        g = torch.Generator(device=dev).manual_seed(0)
+        q = torch.randn(B, Nq, H, D, device=dev, generator=g).to(dt)
+        k = torch.randn(B, Nk, H, D, device=dev, generator=g).to(dt)
+        v = torch.randn(B, Nk, H, D, device=dev, generator=g).to(dt)
+        do = torch.randn(B, Nq, H, D, device=dev, generator=g).to(dt)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        sc = 1.0 / math.sqrt(D)
+        graphs = {}
+        for rate in (0.0, args.dropout):
+            drop = (rate, rng.state, 0)
+            o, lse = ops._fwd(q, k, v, sc, drop=drop)
+            fwd_call = lambda drop=drop: ops._fwd(q, k, v, sc, drop=drop)
+            bwd_call = lambda drop=drop, o=o, lse=lse: ops._bwd(q, k, v, o, lse, do, dq, dk, dv, sc, drop=drop)
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    fwd_call()
+                    bwd_call()
+            torch.cuda.current_stream().wait_stream(s)
+            gf, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gf):
+                for _ in range(reps):
+                    fwd_call()
+            with torch.cuda.graph(gb):
+                for _ in range(reps):
+                    bwd_call()
+            graphs[rate] = (gf, gb)
+        times = {rate: ([], []) for rate in graphs}
+        for _ in range(args.iters):
+            for rate, (gf, gb) in graphs.items():   # the two rates alternate inside every iteration
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                e[0].record()
+                gf.replay()
+                e[1].record()
+                gb.replay()
+                e[2].record()
+                torch.cuda.synchronize()
+                times[rate][0].append(e[0].elapsed_time(e[1]) / reps * 1e3)
+                times[rate][1].append(e[1].elapsed_time(e[2]) / reps * 1e3)
+        med = {rate: tuple(sorted(t)[len(t) // 2] for t in ts) for rate, ts in times.items()}
+        (f0, b0), (f1, b1) = med[0.0], med[args.dropout]
+        r = {"rate": args.dropout, "fwd_us_rate0": round(f0, 1), "bwd_us_rate0": round(b0, 1),
+             "fwd_us": round(f1, 1), "bwd_us": round(b1, 1), "fwd_ratio": round(f1 / f0, 3),
+             "bwd_ratio": round(b1 / b0, 3)}
+        results[shape + "+drop"] = r
+        print(f"{shape:12s} B={B:4d} Nq={Nq:5d} Nk={Nk:5d} H={H:3d} D={D:4d} | rate 0: fwd {f0:8.1f} us bwd {b0:8.1f} us | "
+              f"rate {args.dropout}: fwd {f1:8.1f} us bwd {b1:8.1f} us | ratio fwd {r['fwd_ratio']:.3f} "
+              f"bwd {r['bwd_ratio']:.3f}", flush=True)
 
 
 if __name__ == "__main__":
