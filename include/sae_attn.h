@@ -167,6 +167,33 @@ int sae_attn_dropout_mask(void* stream, int32_t batch, int32_t heads, int32_t se
 /* rng[1] += n on the stream (a one-thread kernel). */
 int sae_dropout_advance(void* stream, uint64_t* rng, uint64_t n);
 
+/* Hidden-state dropout (models/vit.py:12,22,29,47: nn.Dropout(rate = dropout_rate) on the encoder
+   input after the position embedding, on the attention output -- attention.py out_dropout_rate --,
+   on the FF hidden activation after the GELU, ff.py:30, and on the FF output, ff.py:32), on an
+   activation viewed as rows x columns.  T, pk, rng = {seed, offset}, stream_id and (k0, k1) exactly
+   as for the attention mask above; regenerated from counters, nothing stored, and the mask does not
+   depend on the kernel applying it:
+     W              = Philox4x32-10(counter (col >> 4, lo32(row), hi32(row), 1), key (k0, k1))
+     keep(row, col) = ((W[(col >> 2) & 3] >> (8 * (col & 3))) & 0xff) >= T
+     row            = row0 + i * row_step      (64-bit; i = the row the kernel is working on)
+     y              = x * keep / pk
+   One call covers 16 consecutive columns of one row; counter word 3 = 1 separates it from the
+   attention mask (word 3 = 0).  row0 / row_step let a call on a strided subset of the rows (the
+   class-token rows b * N) draw the mask of the full tensor.  A rate below 1 / 512 (T = 0) means no
+   dropout: every entry point below then forwards to the plain one, bit-identically
+   (sae_dropout_rows copies).  rate outside [0, 1) or NaN, rng == NULL, or row_step < 1: SAE_EINVAL,
+   on the host before any HIP call.
+
+   sae_dropout_rows: y = x * keep / pk on [M][C] (dtype bf16 or fp32, row strides ldx / ldy in
+   elements, y may alias x); its backward is the same call on the gradient.  For the paths the
+   fused forms below do not take (fp32 compute dtype, shapes outside an envelope). */
+int sae_dropout_rows(void* stream, int32_t M, int32_t C, int32_t dtype, const void* x, int64_t ldx,
+                     void* y, int64_t ldy, float rate, const uint64_t* rng, uint32_t stream_id,
+                     int64_t row0, int64_t row_step);
+/* keep[M][C] as uint8 0 / 1 by the definition above: what the other entry points apply. */
+int sae_dropout_rows_mask(void* stream, int32_t M, int32_t C, float rate, const uint64_t* rng,
+                          uint32_t stream_id, int64_t row0, int64_t row_step, uint8_t* keep);
+
 /* Talking-heads attention (attention.py:41-58 with talking_heads=True):
      S = scale q k^T ; S1[i] = sum_h th1[h,i] S[h] ; P = softmax(S1) ;
      P2[i] = sum_h th2[h,i] P[h] ; o = P2 v
@@ -248,6 +275,17 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
 #define SAE_NT_ROUTE_GEMM8 3          /* persistent 224/256 x 192 tiles (GELU forward at K < 768: 256 x 128 where that loads the CUs more evenly), LDS-DMA (gemm8_nt_kernel) */
 #define SAE_NT_ROUTE_GEMM8X 4         /* ping-pong 256 x 256 tiles, LDS-DMA (gemm8x_nt_kernel) */
 int sae_gemm_nt_route(int32_t M, int32_t N, int32_t K, int32_t epilogue);
+/* The SAE_EPI_GELU_GRAD forward with the hidden dropout of ff.py:30 (the mask above over [M][N],
+   row = m, col = n, row0 = 0, row_step = 1), h = bf16(acc + bias):
+     c = bf16(gelu(h) * keep / pk),  c2 = bf16(gelu'(h) * keep / pk)
+   each product formed in fp32 and rounded once.  The saved c2 carries the mask, so the input
+   gradient is the unchanged SAE_EPI_MUL_AUX call, and sae_gemm_dw on the dropped c gives the next
+   Dense's weight gradient.  Validation, shape envelope and kernel routing are those of
+   sae_gemm_nt(..., SAE_EPI_GELU_GRAD, ...): sae_gemm_nt_route tells the kernel. */
+int sae_gemm_nt_gelu_dropout(void* stream, int32_t M, int32_t N, int32_t K, const void* a,
+                             int64_t lda, const void* bt, int64_t ldb, const float* bias, void* c,
+                             int64_t ldc, void* c2, float rate, const uint64_t* rng,
+                             uint32_t stream_id);
 /* The same projections at compute dtype float32 (the reference's fp32 trunks, cait.py:147-154,
    and every fp32 run), on the exact-f32 MFMA:
      c[m][n] = (accumulate ? c[m][n] : 0) + sum_k A(m,k) B(k,n) (+ bias[n])
@@ -346,6 +384,20 @@ int sae_layernorm_bwd_scaled(void* stream, int32_t M, int32_t C, const float* x,
                              const void* delta, const float* layerscale, const float* rowscale,
                              int32_t rows_per_sample, float* dlayerscale);
 
+/* The plain add + LayerNorm pair with the hidden dropout on the addend (the attention-output and
+   FF-output dropouts of vit.py:22-24,29-31 riding in the residual add; the mask above over [M][C]):
+     forward   xout = x + delta * keep / pk   (delta required), then the LayerNorm as above
+     backward  ddelta = bf16(dx * keep / pk);  dx, dgamma, dbeta as above */
+int sae_layernorm_fwd_dropout(void* stream, int32_t M, int32_t C, const float* x, const void* delta,
+                              float* xout, const float* gamma, const float* beta, void* y,
+                              float* mean, float* rstd, float eps, float rate, const uint64_t* rng,
+                              uint32_t stream_id, int64_t row0, int64_t row_step);
+int sae_layernorm_bwd_dropout(void* stream, int32_t M, int32_t C, const float* x, const float* mean,
+                              const float* rstd, const float* gamma, const void* dy,
+                              const float* dxin, float* dx, void* ddelta, float* dgamma, float* dbeta,
+                              void* workspace, float rate, const uint64_t* rng, uint32_t stream_id,
+                              int64_t row0, int64_t row_step);
+
 /* Optimizer update of the data-parallel training step (train.py:25-27,229-233: optax.adamw,
    survey D9 descent), every parameter in ONE launch.  The parameters are cut into chunks of
    SAE_ADAMW_CHUNK elements; sae_adamw_plan (host only, no GPU call) fills that chunk table for
@@ -407,6 +459,17 @@ int sae_tokens_fwd(void* stream, int32_t B, int32_t L, int32_t E, const void* to
                    const float* pos, float* x);
 int sae_tokens_bwd(void* stream, int32_t B, int32_t L, int32_t E, const float* dx, void* dtokens, float* dcls,
                    float* dpos);
+
+/* The same with the encoder-input dropout of vit.py:47 (the hidden-state mask above over rows
+   b * (L + 1) + n, columns E):  x = (concat(cls, tokens) + pos) * keep / pk;  backward with
+   g = dx * keep / pk: dtokens = bf16(g[:, 1:]), dpos = sum_b g[b] in the same fixed order,
+   dcls = dpos[0]. */
+int sae_tokens_fwd_dropout(void* stream, int32_t B, int32_t L, int32_t E, const void* tokens,
+                           const float* cls, const float* pos, float* x, float rate,
+                           const uint64_t* rng, uint32_t stream_id);
+int sae_tokens_bwd_dropout(void* stream, int32_t B, int32_t L, int32_t E, const float* dx, void* dtokens,
+                           float* dcls, float* dpos, float rate, const uint64_t* rng,
+                           uint32_t stream_id);
 
 /* Label-smoothed softmax cross entropy of the training step (replaces train.py:77-90:
    optax.smooth_labels(one_hot(labels), alpha) + jnp.mean(optax.softmax_cross_entropy)):

@@ -63,6 +63,15 @@ _PROTOS = [
     ("sae_attn_bwd_dropout", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 10 + [_f32, _vp, ctypes.c_uint32]),
     ("sae_attn_dropout_mask", _i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, ctypes.c_uint32, _vp]),
     ("sae_dropout_advance", _i32, [_vp, _vp, ctypes.c_uint64]),
+    ("sae_dropout_rows", _i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _f32, _vp, ctypes.c_uint32, _i64, _i64]),
+    ("sae_dropout_rows_mask", _i32, [_vp, _i32, _i32, _f32, _vp, ctypes.c_uint32, _i64, _i64, _vp]),
+    ("sae_layernorm_fwd_dropout", _i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
+                                         _f32, _vp, ctypes.c_uint32, _i64, _i64]),
+    ("sae_layernorm_bwd_dropout", _i32, [_vp, _i32, _i32] + [_vp] * 11 + [_f32, _vp, ctypes.c_uint32, _i64, _i64]),
+    ("sae_tokens_fwd_dropout", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, ctypes.c_uint32]),
+    ("sae_tokens_bwd_dropout", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, ctypes.c_uint32]),
+    ("sae_gemm_nt_gelu_dropout", _i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp,
+                                        _f32, _vp, ctypes.c_uint32]),
     ("sae_th_attn_fwd", _i32, [_vp, ctypes.POINTER(SaeAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("sae_th_attn_bwd_workspace_bytes", _sz, [ctypes.POINTER(SaeAttnDesc)]),
     ("sae_th_attn_bwd", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 13),

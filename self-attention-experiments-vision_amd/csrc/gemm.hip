@@ -113,6 +113,7 @@ template <int EPI, class AL> int nt_launch(const NtArgs& g, long long grid, hipS
 }
 // the same tile shape for each epilogue of the 128-row kernel
 template <class AL> int nt_launch_epi(int epilogue, const NtArgs& g, long long grid, hipStream_t st) {
+  if (epilogue == kEpiGeluDrop) return nt_launch<kEpiGeluDrop, AL>(g, grid, st);
   return epilogue == SAE_EPI_NONE   ? nt_launch<kEpiNone, AL>(g, grid, st)
          : epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, AL>(g, grid, st)
                                     : nt_launch<kEpiDGelu, AL>(g, grid, st);
@@ -392,9 +393,11 @@ int sae_gemm_nt_route(int32_t M, int32_t N, int32_t K, int32_t epilogue) {
   return nt_plan(M, N, K, epilogue).route;
 }
 
-int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* bt,
-                int64_t ldb, const float* bias, void* c, int64_t ldc, int32_t epilogue, const void* aux,
-                int64_t ldaux, void* c2) {
+// drop != nullptr (epilogue SAE_EPI_GELU_GRAD): the kEpiGeluDrop instance of the kernel nt_plan routes
+// the plain call to -- same validation, same shape envelope, same route
+static int gemm_nt_impl(void* stream, int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* bt,
+                        int64_t ldb, const float* bias, void* c, int64_t ldc, int32_t epilogue, const void* aux,
+                        int64_t ldaux, void* c2, const DropRows* drop) {
   if (M < 1 || N < 1 || K < 1) return fail(SAE_EINVAL, "gemm_nt: M/N/K must be >= 1 (got %d/%d/%d)", M, N, K);
   if (K % 8 || N % 8) return fail(SAE_EUNSUPPORTED, "gemm_nt: K (%d) and N (%d) must be multiples of 8", K, N);
   if (lda < K || ldb < K || ldc < N || lda % 8 || ldb % 8 || ldc % 8)
@@ -429,6 +432,13 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
   g.ldc = ldc;
   g.ldaux = ldaux;
   hipStream_t st = (hipStream_t)stream;
+  if (drop) {
+    g.drop = *drop;
+    if (p.route == SAE_NT_ROUTE_GEMM8X) return g8x_launch<kEpiGeluDrop, 256>(g, st);
+    if (p.route == SAE_NT_ROUTE_GEMM8)
+      return p.bn128 ? g8_launch_bm<kEpiGeluDrop, 128, 64, 2, 256, 4>(g, st) : g8_launch<kEpiGeluDrop, 192, 64, 2>(g, st);
+    epilogue = kEpiGeluDrop;   // the 128-row kernel, tile shape by the plan below
+  }
   if (p.route == SAE_NT_ROUTE_GEMM8X)
     return epilogue == SAE_EPI_NONE ? g8x_launch<kEpiNone, 256>(g, st) : g8x_launch<kEpiGelu, 256>(g, st);
   if (p.route == SAE_NT_ROUTE_GEMM8) {
@@ -447,9 +457,26 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
   if (p.route == SAE_NT_ROUTE_TILE128_KTAIL) return nt_launch_epi<NtRowAT<64, 128, true>>(epilogue, g, grid128, st);
   if (p.tall) return nt_launch_epi<NtRowAT<32, 256>>(epilogue, g, (long long)((M + 255) / 256) * tn, st);
   if (p.shallow)
-    return epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, NtRowAT<32>>(g, grid128, st)
-                                    : nt_launch<kEpiDGelu, NtRowAT<32>>(g, grid128, st);
+    return epilogue == kEpiGeluDrop  ? nt_launch<kEpiGeluDrop, NtRowAT<32>>(g, grid128, st)
+           : epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, NtRowAT<32>>(g, grid128, st)
+                                      : nt_launch<kEpiDGelu, NtRowAT<32>>(g, grid128, st);
   return nt_launch_epi<NtRowAT<64>>(epilogue, g, grid128, st);
+}
+
+int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* bt,
+                int64_t ldb, const float* bias, void* c, int64_t ldc, int32_t epilogue, const void* aux,
+                int64_t ldaux, void* c2) {
+  return gemm_nt_impl(stream, M, N, K, a, lda, bt, ldb, bias, c, ldc, epilogue, aux, ldaux, c2, nullptr);
+}
+
+int sae_gemm_nt_gelu_dropout(void* stream, int32_t M, int32_t N, int32_t K, const void* a, int64_t lda,
+                             const void* bt, int64_t ldb, const float* bias, void* c, int64_t ldc, void* c2,
+                             float rate, const uint64_t* rng, uint32_t stream_id) {
+  unsigned thr;
+  if (int rc = rows_drop_check("gemm_nt_gelu_dropout", rate, rng, 1, &thr)) return rc;
+  if (thr == 0) return sae_gemm_nt(stream, M, N, K, a, lda, bt, ldb, bias, c, ldc, SAE_EPI_GELU_GRAD, nullptr, 0, c2);
+  const DropRows d = make_drop_rows(rng, stream_id, thr, 0, 1);
+  return gemm_nt_impl(stream, M, N, K, a, lda, bt, ldb, bias, c, ldc, SAE_EPI_GELU_GRAD, nullptr, 0, c2, &d);
 }
 
 int sae_patch_embed_fwd(void* stream, const sae_patch_desc* d, const void* images, const void* wt, const float* bias,

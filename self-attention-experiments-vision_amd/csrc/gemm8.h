@@ -200,6 +200,8 @@ __global__ __launch_bounds__(512, 1) void gemm8_nt_kernel(NtArgs a) {
   constexpr int SCH = C::WN / 8;                  // 16-byte chunks per tile row
   uint4 hv[EPI == kEpiDGelu ? (C::MT + 1) / 2 : 1][EPI == kEpiDGelu ? 32 * SCH / 64 : 1];   // GELU' aux tile
   char* scratch = smem + g8_ring_bytes<BN, BK, NS>() + w * g8_scratch_bytes<BN, WGM>();
+  DropKey dk = {};
+  if constexpr (EPI == kEpiGeluDrop) dk = drop_key(a.drop.rng, a.drop.stream_id);
 
   if (total > 0) set_issue_tile(0);
 #pragma unroll
@@ -327,8 +329,15 @@ __global__ __launch_bounds__(512, 1) void gemm8_nt_kernel(NtArgs a) {
         }
       }
       __builtin_amdgcn_wave_barrier();
+      constexpr int ITS = 32 * SCH / 64;   // store rounds of a 32-row group
+      unsigned dw[EPI == kEpiGeluDrop ? ITS : 1][2];
+      if constexpr (EPI == kEpiGeluDrop)
+        drop_round_words<ITS>(dk, lane, [&](int it) {
+          const int id = it * 64 + lane;
+          return int2{m0 + 32 * ip + id / SCH, nw + 8 * (id % SCH)};
+        }, dw);
 #pragma unroll
-      for (int it = 0; it < 32 * SCH / 64; ++it) {
+      for (int it = 0; it < ITS; ++it) {
         const int id = it * 64 + lane;
         const int rr = id / SCH, c = id % SCH;
         const uint4 raw = *reinterpret_cast<const uint4*>(scratch + rr * SRB + 16 * c);
@@ -339,10 +348,12 @@ __global__ __launch_bounds__(512, 1) void gemm8_nt_kernel(NtArgs a) {
           if (a.nts & 1) {   // (wave-uniform)
             if constexpr (EPI == kEpiNone) st16<true>(cp, raw);
             else if constexpr (EPI == kEpiGelu) gelu_store8<true>(raw, a.gp, cp, a.c2 + (long long)m * a.ldc + n);
+            else if constexpr (EPI == kEpiGeluDrop) gelu_drop_store8<true>(raw, dw[EPI == kEpiGeluDrop ? it : 0][0], dw[EPI == kEpiGeluDrop ? it : 0][1], a.drop, cp, a.c2 + (long long)m * a.ldc + n);
             else st16<true>(cp, dgelu8(raw, hv[ip][it], a.gp));
           } else {
             if constexpr (EPI == kEpiNone) st16(cp, raw);
             else if constexpr (EPI == kEpiGelu) gelu_store8(raw, a.gp, cp, a.c2 + (long long)m * a.ldc + n);
+            else if constexpr (EPI == kEpiGeluDrop) gelu_drop_store8(raw, dw[EPI == kEpiGeluDrop ? it : 0][0], dw[EPI == kEpiGeluDrop ? it : 0][1], a.drop, cp, a.c2 + (long long)m * a.ldc + n);
             else st16(cp, dgelu8(raw, hv[ip][it], a.gp));
           }
         }
@@ -510,6 +521,25 @@ __global__ __launch_bounds__(512, 1) void gemm8x_nt_kernel(NtArgs a) {
     }
   __builtin_amdgcn_wave_barrier();
   const int mw = m0 + C::WM * grp;
+  if constexpr (EPI == kEpiGeluDrop) {   // the store rounds in pairs (drop_round_words)
+    static_assert(C::WM * SCH / 64 % 2 == 0 && SCH == 8, "whole pairs of rounds; lane -> (row, chunk) below");
+    const DropKey dk = drop_key(a.drop.rng, a.drop.stream_id);
+    const int n = nw + 8 * (lane & 7);
+#pragma unroll 2
+    for (int it0 = 0; it0 < C::WM * SCH / 64; it0 += 2) {
+      unsigned dw[2][2];
+      drop_round_words<2>(dk, lane, [&](int j) { return int2{mw + 8 * (it0 + j) + (lane >> 3), n}; }, dw);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int rr = 8 * (it0 + j) + (lane >> 3), m = mw + rr;
+        const uint4 raw = *reinterpret_cast<const uint4*>(scratch + rr * SRB + 16 * (lane & 7));
+        if (m < a.M && n < a.N)
+          gelu_drop_store8(raw, dw[j][0], dw[j][1], a.drop, a.c + (long long)m * a.ldc + n,
+                           a.c2 + (long long)m * a.ldc + n);
+      }
+    }
+    return;
+  }
 #pragma unroll 4
   for (int it = 0; it < C::WM * SCH / 64; ++it) {
     const int id = it * 64 + lane;

@@ -15,6 +15,9 @@
 // backward epilogue is one multiply, c = bf16(bf16(acc) * g): the sigmoid / rcp work of GELU'
 // leaves the input-gradient GEMM, whose epilogue bounded it.
 // which removes the two elementwise HBM passes (GELU forward, GELU backward) per FF block.
+//   kEpiGeluDrop: the gp forward with the hidden dropout of ff.py:30 (drop_rows.h over [M][N]):
+//     c = bf16(gelu(h) * keep / pk), c2 = bf16(gelu'(h) * keep / pk) -- the saved c2 carries the
+//     mask, so the backward is the unchanged multiply epilogue.
 //
 // Structure (gfx950): a 128 x 128 output tile per 256-thread workgroup, 4 waves of 64 x 64 (2 x 2
 // v_mfma_f32_32x32x16_bf16 accumulators); BK-deep K stages staged global -> registers -> LDS
@@ -28,10 +31,11 @@
 // fetched from HBM once per XCD; the small weight stays L2-resident).
 #pragma once
 #include "common.h"
+#include "drop_rows.h"
 
 namespace sae {
 
-enum { kEpiNone = 0, kEpiGelu = 1, kEpiDGelu = 2 };
+enum { kEpiNone = 0, kEpiGelu = 1, kEpiDGelu = 2, kEpiGeluDrop = 3 };
 
 struct NtArgs {
   const __bf16* a;     // [M][K], row stride lda
@@ -46,6 +50,7 @@ struct NtArgs {
   int gp;              // kEpiGelu: c2 = gelu'(h) instead of h; kEpiDGelu: aux holds gelu'(h)
   int nts;             // gemm8: 1 = epilogue stores non-temporal (streamed past L2's normal
                        // allocation), 2 = the gelu' aux tile loaded non-temporal
+  DropRows drop;       // kEpiGeluDrop (row0 = 0, row_step = 1: the row is the output row m)
 };
 
 constexpr int kNtT = 128;   // output tile edge
@@ -128,6 +133,55 @@ __device__ __forceinline__ void gelu_store8(const uint4& raw, bool gp, __bf16* c
     st16<NT>(c2, raw);
     st16<NT>(c, uint4{gelu_bf2(raw.x), gelu_bf2(raw.y), gelu_bf2(raw.z), gelu_bf2(raw.w)});
   }
+}
+// kEpiGeluDrop: a store round gives a lane the 8 outputs n .. n + 7 (n % 8 == 0) of one row m, half a
+// Philox block -- words 0, 1 (n % 16 == 0) or 2, 3 of the call.  In every kernel's store rounds lanes
+// 2 j and 2 j + 1 hold the two halves of one block (lane parity = (n >> 3) & 1, same row), so the
+// rounds are taken in pairs: the even lane runs the call of round 2 p, the odd lane that of round
+// 2 p + 1, and each hands the partner its half by DPP quad_perm -- one call per 16 outputs, none
+// wasted (an odd last round: the odd lanes' call is unused).  Per output beyond the gp epilogue:
+// 1 / 16 of a call (ten rounds of 4 multiplies, 4 xors, 2 adds) plus a byte extract, compare, select
+// and 2 multiplies; each product is formed in fp32 and rounded once.
+// pos(it) = this lane's (m, n) of round it.  Every lane of the wave must be executing: call it before
+// the rounds' bounds checks.
+template <int ITS, class Pos>
+__device__ __forceinline__ void drop_round_words(const DropKey& dk, int lane, Pos&& pos, unsigned (&w)[ITS][2]) {
+  const bool odd = lane & 1;
+#pragma unroll
+  for (int p = 0; p < (ITS + 1) / 2; ++p) {
+    const int ia = 2 * p, ib = 2 * p + 1 < ITS ? 2 * p + 1 : 2 * p;
+    const int2 mine = pos(odd ? ib : ia);
+    const uint4 c = drop_rows_call(dk, (unsigned long long)mine.x, (unsigned)mine.y >> 4);
+    // the partner's half of this lane's call: an odd partner takes words 2, 3, an even one words 0, 1
+    const unsigned r0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? c.x : c.z), 0xB1, 0xf, 0xf, false);
+    const unsigned r1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? c.y : c.w), 0xB1, 0xf, 0xf, false);
+    w[ia][0] = odd ? r0 : c.x;
+    w[ia][1] = odd ? r1 : c.y;
+    if (2 * p + 1 < ITS) {
+      w[ib][0] = odd ? c.z : r0;
+      w[ib][1] = odd ? c.w : r1;
+    }
+  }
+}
+__device__ __forceinline__ unsigned gelu_grad_drop_bf2(unsigned hw, f32x2 sc, unsigned& gw) {
+  const f32x2 x = bf2_to_f2(hw);
+  const f32x2 s = gelu_sig2(x);
+  const f32x2 q = s - s * s;
+  const f32x2 poly = (2.f * kGeluB) + (6.f * kGeluB * kGeluK) * (x * x);
+  gw = f2_to_bf2(((x * q) * poly + s) * sc);
+  return f2_to_bf2((x * s) * sc);
+}
+template <bool NT = false>
+__device__ __forceinline__ void gelu_drop_store8(const uint4& raw, unsigned wa, unsigned wb, const DropRows& d,
+                                                 __bf16* c, __bf16* c2) {
+  const f32x4 sa = drop_scale4(wa, d.thr, d.inv), sb = drop_scale4(wb, d.thr, d.inv);
+  uint4 g, y;
+  y.x = gelu_grad_drop_bf2(raw.x, f32x2{sa[0], sa[1]}, g.x);
+  y.y = gelu_grad_drop_bf2(raw.y, f32x2{sa[2], sa[3]}, g.y);
+  y.z = gelu_grad_drop_bf2(raw.z, f32x2{sb[0], sb[1]}, g.z);
+  y.w = gelu_grad_drop_bf2(raw.w, f32x2{sb[2], sb[3]}, g.w);
+  st16<NT>(c2, g);
+  st16<NT>(c, y);
 }
 __device__ __forceinline__ uint4 dgelu8(const uint4& raw, const uint4& hv, bool gp) {
   if (gp) return uint4{mul_bf2(raw.x, hv.x), mul_bf2(raw.y, hv.y), mul_bf2(raw.z, hv.z), mul_bf2(raw.w, hv.w)};
@@ -332,6 +386,8 @@ __global__ __launch_bounds__(256, (nt_min_blocks<EPI, AL>())) void gemm_nt_kerne
       }
   }
   char* scratch = smem + w * (32 * 64 * 2);   // 4 KiB per wave; the stage buffers are free now
+  DropKey dk = {};
+  if constexpr (EPI == kEpiGeluDrop) dk = drop_key(a.drop.rng, a.drop.stream_id);
   typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 #pragma unroll
   for (int u = 0; u < UM; ++u) {
@@ -345,6 +401,9 @@ __global__ __launch_bounds__(256, (nt_min_blocks<EPI, AL>())) void gemm_nt_kerne
         *reinterpret_cast<bf16x4*>(scratch + r * 128 + 16 * ((4 * t + g) ^ swz<64>(r)) + 8 * h) = v;
       }
     __builtin_amdgcn_wave_barrier();
+    unsigned dw[EPI == kEpiGeluDrop ? 4 : 1][2];
+    if constexpr (EPI == kEpiGeluDrop)
+      drop_round_words<4>(dk, lane, [&](int it) { return int2{m0 + WT * wm + 32 * u + 8 * it + (lane >> 3), n}; }, dw);
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int rr = 8 * it + (lane >> 3);
@@ -356,6 +415,9 @@ __global__ __launch_bounds__(256, (nt_min_blocks<EPI, AL>())) void gemm_nt_kerne
           *reinterpret_cast<uint4*>(a.c + orow * a.ldc + n) = raw;
         } else if constexpr (EPI == kEpiGelu) {
           gelu_store8(raw, a.gp, a.c + orow * a.ldc + n, a.c2 + orow * a.ldc + n);
+        } else if constexpr (EPI == kEpiGeluDrop) {
+          gelu_drop_store8(raw, dw[EPI == kEpiGeluDrop ? it : 0][0], dw[EPI == kEpiGeluDrop ? it : 0][1], a.drop,
+                           a.c + orow * a.ldc + n, a.c2 + orow * a.ldc + n);
         } else {
           *reinterpret_cast<uint4*>(a.c + orow * a.ldc + n) = dgelu8(raw, auxv[UM == 2 ? u : 0][it], a.gp);
         }

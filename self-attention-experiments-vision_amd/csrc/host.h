@@ -87,6 +87,17 @@ inline int elem_size(int dtype) { return dtype == SAE_DTYPE_BF16 ? 2 : 4; }
 
 inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
 
+// Arguments of the hidden-state dropout entry points (drop_rows.h), checked before any HIP call:
+// *thr = T = clamp(lrintf(rate * 256), 0, 255); T == 0 (a rate below 1 / 512) means no dropout and
+// the caller forwards to the plain entry point.
+inline int rows_drop_check(const char* what, float rate, const uint64_t* rng, int64_t row_step, unsigned* thr) {
+  if (!(rate >= 0.f && rate < 1.f)) return fail(SAE_EINVAL, "%s: dropout rate %g is outside [0, 1)", what, (double)rate);
+  if (!rng) return fail(SAE_EINVAL, "%s: rng must be non-NULL", what);
+  if (row_step < 1) return fail(SAE_EINVAL, "%s: row_step (%lld) must be >= 1", what, (long long)row_step);
+  *thr = (unsigned)std::min(255L, std::max(0L, lrintf(rate * 256.f)));
+  return SAE_OK;
+}
+
 inline int pick_dp(int D) { return D <= 32 ? 32 : (D <= 64 ? 64 : (D <= 128 ? 128 : 0)); }
 
 inline bool strides_vec(const int64_t* s, int epc) { return s[0] % epc == 0 && s[1] % epc == 0 && s[2] % epc == 0; }

@@ -13,6 +13,7 @@
 // One wave per row (C <= 1024 columns, float4 per lane), rows strided over the grid; HBM-bound.
 #pragma once
 #include "common.h"
+#include "drop_rows.h"
 
 namespace sae {
 
@@ -42,6 +43,9 @@ struct LnArgs {
   int rpb;               // rows per sample
   int M, C, nblk;
   float eps;
+  // hidden-state dropout of the addend (drop_rows.h; the DROP instances only):
+  // x_out = x + delta * keep / pk over rows row0 + row * row_step
+  DropRows drop;
 };
 
 constexpr int kLnMaxV = 4;   // float4 chunks per lane: C <= 1024
@@ -72,7 +76,9 @@ __device__ __forceinline__ f32x4 ln_bf16r(f32x4 v) {
 // Rows are software-pipelined: the next row's x / delta loads are issued before this row's
 // reductions, so each wave keeps two rows of loads in flight (one row at a time left the HBM
 // latency exposed between rows: 5.3 of 8 TB/s).
-template <int NV>
+// DROP: the addend is dropped as it is added (one Philox call per lane and row, issued after the
+// next row's loads; the words cross the quad by DPP, drop_wave_words)
+template <int NV, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs a) {
   typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
   const int lane = threadIdx.x & 63;
@@ -94,6 +100,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs a) {
   }
   const float invC = 1.f / (float)a.C;
   const bool hasd = a.delta != nullptr;
+  DropKey dk = {};
+  if constexpr (DROP) dk = drop_key(a.drop.rng, a.drop.stream_id);
   f32x4 nx[NV];    // the next row's x and delta, in flight during this row
   bf16x4 nd[NV];
   auto load = [&](int row) {
@@ -124,12 +132,19 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs a) {
       load(row + nw);
       if (a.rsc) nsf = a.rsc[(row + nw) / a.rpb];
     }
+    unsigned dw[NV];
+    if constexpr (DROP)
+      drop_wave_words<NV>(dk, (unsigned long long)(a.drop.row0 + (long long)row * a.drop.row_step), lane, dw);
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int c = lane + 64 * k;
       if (c < C4 && hasd) {
-        v[k] += f32x4{(float)dv[k][0], (float)dv[k][1], (float)dv[k][2], (float)dv[k][3]} * (ls[k] * rsf);
+        if constexpr (DROP)
+          v[k] += f32x4{(float)dv[k][0], (float)dv[k][1], (float)dv[k][2], (float)dv[k][3]} *
+                  drop_scale4(dw[k], a.drop.thr, a.drop.inv);
+        else
+          v[k] += f32x4{(float)dv[k][0], (float)dv[k][1], (float)dv[k][2], (float)dv[k][3]} * (ls[k] * rsf);
         reinterpret_cast<f32x4*>(a.xout + ro)[c] = v[k];
       }
       s += v[k][0] + v[k][1] + v[k][2] + v[k][3];
@@ -158,8 +173,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs a) {
 }
 
 // NP = 2: dgamma / dbeta partials; NP = 3: also the LayerScale gradient (a.lsc, a.delta set)
-template <int NV, int NP = 2>
+// DROP (NP = 2): ddelta = bf16(dx * keep / pk), the forward's mask regenerated
+template <int NV, int NP = 2, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs a) {
+  static_assert(!DROP || NP == 2, "the dropout form has no LayerScale");
   typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
   __shared__ f32x4 red[4][NP][64 * NV];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -176,6 +193,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs a) {
   }
   const float invC = 1.f / (float)a.C;
   const bool hasin = a.dxin != nullptr;
+  DropKey dk = {};
+  if constexpr (DROP) dk = drop_key(a.drop.rng, a.drop.stream_id);
   // the next row's dy / x / dx_in (and mean / rstd; NP = 3: delta and the row scale), in flight
   // during this row (as ln_fwd_kernel)
   bf16x4 ndy[NV], nde[NP == 3 ? NV : 1];
@@ -228,6 +247,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs a) {
       s2 += t[0] + t[1] + t[2] + t[3];
     }
     const float m1 = ln_wave_sum(s1) * invC, m2 = ln_wave_sum(s2) * invC;
+    unsigned dw[NV];
+    if constexpr (DROP)
+      drop_wave_words<NV>(dk, (unsigned long long)(a.drop.row0 + (long long)row * a.drop.row_step), lane, dw);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int c = lane + 64 * k;
@@ -238,6 +260,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs a) {
         if constexpr (NP == 3) {   // x_out = x + delta * ls * rsf
           pl[k] += d * f32x4{(float)der[k][0], (float)der[k][1], (float)der[k][2], (float)der[k][3]} * rsf;
           if (a.ddelta) st_bf16x4(a.ddelta + ro + 4 * c, d * ls[k] * rsf);
+        } else if constexpr (DROP) {
+          if (a.ddelta) st_bf16x4(a.ddelta + ro + 4 * c, d * drop_scale4(dw[k], a.drop.thr, a.drop.inv));
         } else {
           if (a.ddelta) st_bf16x4(a.ddelta + ro + 4 * c, d);
         }

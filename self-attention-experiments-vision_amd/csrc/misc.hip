@@ -1,11 +1,67 @@
 // misc.hip -- the rest of the C ABI: residual add + LayerNorm (ln.h), the encoder input tokens
-// (tokens.h), the smoothed cross-entropy (loss.h), AdamW (adamw.h), the stream utilities of
-// bench.py, and the library's error string and version.
+// (tokens.h), the hidden-state dropout of row-major activations (drop_rows.h: their dropout forms
+// and the standalone kernels), the smoothed cross-entropy (loss.h), AdamW (adamw.h), the stream
+// utilities of bench.py, and the library's error string and version.
 #include "ln.h"
 #include "loss.h"
 #include "tokens.h"
 #include "adamw.h"
 #include "host.h"
+
+namespace sae {
+
+// ------------------------------------------------------------------------ standalone kernels
+// y = x * keep / pk on [M][C] (row strides ldx / ldy; y may alias x): the paths the fused forms do
+// not take (fp32 compute dtype, shapes outside an envelope) and its own backward.  One thread per
+// 4 consecutive columns (one Philox word); HBM-bound.  vec (set by the host: C and both strides
+// multiples of 4, both pointers aligned to 4 elements): one vector load and store per thread.
+struct DropRowsArgs {
+  const void* x;
+  void* y;
+  unsigned char* keep;   // the mask kernel's output [M][C]
+  long long ldx, ldy;
+  int M, C, vec;
+  DropRows d;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_rows_kernel(DropRowsArgs a) {
+  const int C4 = (a.C + 3) / 4;
+  const long long total = (long long)a.M * C4;
+  const DropKey dk = drop_key(a.d.rng, a.d.stream_id);
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int c4 = (int)(i % C4);
+    const long long r = i / C4;
+    const unsigned long long row = (unsigned long long)(a.d.row0 + r * a.d.row_step);
+    const unsigned w = drop_word(drop_rows_call(dk, row, (unsigned)c4 >> 2), (unsigned)c4 & 3u);
+    const f32x4 s = drop_scale4(w, a.d.thr, a.d.inv);
+    const T* xp = reinterpret_cast<const T*>(a.x) + r * a.ldx + 4 * c4;
+    T* yp = reinterpret_cast<T*>(a.y) + r * a.ldy + 4 * c4;
+    if (a.vec) {
+      typedef __attribute__((ext_vector_type(4))) T vec4;
+      const vec4 v = *reinterpret_cast<const vec4*>(xp);
+      *reinterpret_cast<vec4*>(yp) = vec4{(T)((float)v[0] * s[0]), (T)((float)v[1] * s[1]), (T)((float)v[2] * s[2]),
+                                          (T)((float)v[3] * s[3])};
+      continue;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * c4 + e < a.C) yp[e] = (T)((float)xp[e] * s[e]);
+  }
+}
+
+// keep[M][C] as uint8 0 / 1: one thread per element (a test and debugging aid)
+__global__ __launch_bounds__(256) void dropout_rows_mask_kernel(DropRowsArgs a) {
+  const long long total = (long long)a.M * a.C;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const DropKey dk = drop_key(a.d.rng, a.d.stream_id);
+  const unsigned col = (unsigned)(i % a.C);
+  const long long r = i / a.C;
+  a.keep[i] = drop_rows_keep(dk, a.d.thr, (unsigned long long)(a.d.row0 + r * a.d.row_step), col) ? 1 : 0;
+}
+
+}  // namespace sae
 
 using namespace sae;
 
@@ -27,9 +83,10 @@ int ln_check(int32_t M, int32_t C) {
   return SAE_OK;
 }
 
+// drop != nullptr: the dropout form (lsc / rsc unused)
 int ln_fwd_impl(void* stream, int32_t M, int32_t C, const float* x, const void* delta, float* xout,
                 const float* gamma, const float* beta, void* y, float* mean, float* rstd, float eps,
-                const float* lsc, const float* rsc, int32_t rpb) {
+                const float* lsc, const float* rsc, int32_t rpb, const DropRows* drop = nullptr) {
   if (int rc = ln_check(M, C)) return rc;
   if (!x || !gamma || !beta || !y || !mean || !rstd) return fail(SAE_EINVAL, "layernorm_fwd: NULL argument");
   if ((delta == nullptr) != (xout == nullptr))
@@ -56,14 +113,20 @@ int ln_fwd_impl(void* stream, int32_t M, int32_t C, const float* x, const void* 
   int lnb = ln_fwd_blocks(M);
   if (int v = dev_knob("SAE_LN_FWD_BLOCKS")) lnb = std::max(1, std::min((M + 3) / 4, v));
   void (*const fn[4])(LnArgs) = {ln_fwd_kernel<1>, ln_fwd_kernel<2>, ln_fwd_kernel<3>, ln_fwd_kernel<4>};
+  void (*const fnd[4])(LnArgs) = {ln_fwd_kernel<1, true>, ln_fwd_kernel<2, true>, ln_fwd_kernel<3, true>,
+                                  ln_fwd_kernel<4, true>};
   const int nv = (C / 4 + 63) / 64;   // 1 .. kLnMaxV (ln_check)
+  if (drop) {
+    a.drop = *drop;
+    return launch("layernorm_fwd_dropout", fnd[nv - 1], (long long)lnb, dim3(256), 0, (hipStream_t)stream, a);
+  }
   return launch("layernorm_fwd", fn[nv - 1], (long long)lnb, dim3(256), 0, (hipStream_t)stream, a);
 }
 
 int ln_bwd_impl(void* stream, int32_t M, int32_t C, const float* x, const float* mean, const float* rstd,
                 const float* gamma, const void* dy, const float* dxin, float* dx, void* ddelta,
                 float* dgamma, float* dbeta, void* workspace, const void* delta, const float* lsc,
-                const float* rsc, int32_t rpb, float* dlsc) {
+                const float* rsc, int32_t rpb, float* dlsc, const DropRows* drop = nullptr) {
   if (int rc = ln_check(M, C)) return rc;
   if (!x || !mean || !rstd || !gamma || !dy || !dx || !dgamma || !dbeta || !workspace)
     return fail(SAE_EINVAL, "layernorm_bwd: NULL argument");
@@ -96,8 +159,13 @@ int ln_bwd_impl(void* stream, int32_t M, int32_t C, const float* x, const float*
   const bool sc = lsc != nullptr;   // the scaled form: three partial rows (dgamma, dbeta, dlayerscale)
   void (*const fn[4][2])(LnArgs) = {{ln_bwd_kernel<1, 2>, ln_bwd_kernel<1, 3>}, {ln_bwd_kernel<2, 2>, ln_bwd_kernel<2, 3>},
                                     {ln_bwd_kernel<3, 2>, ln_bwd_kernel<3, 3>}, {ln_bwd_kernel<4, 2>, ln_bwd_kernel<4, 3>}};
+  void (*const fnd[4])(LnArgs) = {ln_bwd_kernel<1, 2, true>, ln_bwd_kernel<2, 2, true>, ln_bwd_kernel<3, 2, true>,
+                                  ln_bwd_kernel<4, 2, true>};
   const int nv = (C / 4 + 63) / 64;   // 1 .. kLnMaxV (ln_check)
-  if (int rc = launch("layernorm_bwd", fn[nv - 1][sc], (long long)a.nblk, dim3(256), 0, st, a)) return rc;
+  if (drop) a.drop = *drop;
+  if (int rc = drop ? launch("layernorm_bwd_dropout", fnd[nv - 1], (long long)a.nblk, dim3(256), 0, st, a)
+                    : launch("layernorm_bwd", fn[nv - 1][sc], (long long)a.nblk, dim3(256), 0, st, a))
+    return rc;
   const long long rg = ((sc ? 3 : 2) * (C / 4) + kLnRedCols - 1) / kLnRedCols;
   return launch("layernorm_bwd_reduce", sc ? ln_bwd_reduce_kernel<3> : ln_bwd_reduce_kernel<2>, rg, dim3(256), 0, st, a);
 }
@@ -107,6 +175,38 @@ int tokens_check(int32_t B, int32_t L, int32_t E) {
   if (B < 1 || L < 1 || E < 4 || E % 4 || E > 4096)
     return fail(SAE_EINVAL, "tokens: B %d, L %d, E %d (E a multiple of 4, <= 4096)", B, L, E);
   return 0;
+}
+
+// drop != nullptr: the dropout forms
+int tokens_fwd_impl(void* stream, int32_t B, int32_t L, int32_t E, const void* tokens, const float* cls,
+                    const float* pos, float* x, const DropRows* drop) {
+  if (int rc = tokens_check(B, L, E)) return rc;
+  if (!tokens || !cls || !pos || !x) return fail(SAE_EINVAL, "tokens_fwd: NULL argument");
+  if (!aligned16(cls) || !aligned16(pos) || !aligned16(x) || ((uintptr_t)tokens & 7))
+    return fail(SAE_EINVAL, "tokens_fwd: cls / pos / x need 16-byte, tokens 8-byte alignment");
+  const long long total = (long long)B * (L + 1) * (E / 4);
+  const long long grid = std::min<long long>((total + 255) / 256, 8192);
+  if (drop)
+    return launch("tokens_fwd_dropout", tokens_fwd_drop_kernel, grid, dim3(256), 0, (hipStream_t)stream,
+                  reinterpret_cast<const __bf16*>(tokens), cls, pos, x, B, L, E, *drop);
+  return launch("tokens_fwd", tokens_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream,
+                reinterpret_cast<const __bf16*>(tokens), cls, pos, x, B, L, E);
+}
+
+int tokens_bwd_impl(void* stream, int32_t B, int32_t L, int32_t E, const float* dx, void* dtokens, float* dcls,
+                    float* dpos, const DropRows* drop) {
+  if (int rc = tokens_check(B, L, E)) return rc;
+  if (!dx || !dtokens || !dpos) return fail(SAE_EINVAL, "tokens_bwd: NULL argument");
+  if (!aligned16(dx) || !aligned16(dpos) || (dcls && !aligned16(dcls)) || ((uintptr_t)dtokens & 7))
+    return fail(SAE_EINVAL, "tokens_bwd: dx / dcls / dpos need 16-byte, dtokens 8-byte alignment");
+  const int E4 = E / 4;
+  const int G = std::max(1, std::min(B, 512 / E4));
+  if (drop)
+    return launch("tokens_bwd_dropout", tokens_bwd_drop_kernel, (long long)L + 1, dim3((unsigned)(G * E4)),
+                  (size_t)G * E4 * 16, (hipStream_t)stream, dx, reinterpret_cast<__bf16*>(dtokens), dcls, dpos, B, L,
+                  E, *drop);
+  return launch("tokens_bwd", tokens_bwd_kernel, (long long)L + 1, dim3((unsigned)(G * E4)), (size_t)G * E4 * 16,
+                (hipStream_t)stream, dx, reinterpret_cast<__bf16*>(dtokens), dcls, dpos, B, L, E);
 }
 
 // ------------------------------------------------------------------ training loss
@@ -168,25 +268,98 @@ int sae_layernorm_bwd_scaled(void* stream, int32_t M, int32_t C, const float* x,
 
 int sae_tokens_fwd(void* stream, int32_t B, int32_t L, int32_t E, const void* tokens, const float* cls,
                    const float* pos, float* x) {
-  if (int rc = tokens_check(B, L, E)) return rc;
-  if (!tokens || !cls || !pos || !x) return fail(SAE_EINVAL, "tokens_fwd: NULL argument");
-  if (!aligned16(cls) || !aligned16(pos) || !aligned16(x) || ((uintptr_t)tokens & 7))
-    return fail(SAE_EINVAL, "tokens_fwd: cls / pos / x need 16-byte, tokens 8-byte alignment");
-  const long long total = (long long)B * (L + 1) * (E / 4);
-  return launch("tokens_fwd", tokens_fwd_kernel, std::min<long long>((total + 255) / 256, 8192), dim3(256), 0,
-                (hipStream_t)stream, reinterpret_cast<const __bf16*>(tokens), cls, pos, x, B, L, E);
+  return tokens_fwd_impl(stream, B, L, E, tokens, cls, pos, x, nullptr);
 }
 
 int sae_tokens_bwd(void* stream, int32_t B, int32_t L, int32_t E, const float* dx, void* dtokens, float* dcls,
                    float* dpos) {
-  if (int rc = tokens_check(B, L, E)) return rc;
-  if (!dx || !dtokens || !dpos) return fail(SAE_EINVAL, "tokens_bwd: NULL argument");
-  if (!aligned16(dx) || !aligned16(dpos) || (dcls && !aligned16(dcls)) || ((uintptr_t)dtokens & 7))
-    return fail(SAE_EINVAL, "tokens_bwd: dx / dcls / dpos need 16-byte, dtokens 8-byte alignment");
-  const int E4 = E / 4;
-  const int G = std::max(1, std::min(B, 512 / E4));
-  return launch("tokens_bwd", tokens_bwd_kernel, (long long)L + 1, dim3((unsigned)(G * E4)), (size_t)G * E4 * 16,
-                (hipStream_t)stream, dx, reinterpret_cast<__bf16*>(dtokens), dcls, dpos, B, L, E);
+  return tokens_bwd_impl(stream, B, L, E, dx, dtokens, dcls, dpos, nullptr);
+}
+
+// ------------------------------------------------------------------ hidden-state dropout
+// Every entry point checks rate / rng / row_step first (no HIP call before), and forwards to the
+// plain entry point when the rate quantises to T = 0.
+int sae_dropout_rows(void* stream, int32_t M, int32_t C, int32_t dtype, const void* x, int64_t ldx, void* y,
+                     int64_t ldy, float rate, const uint64_t* rng, uint32_t stream_id, int64_t row0,
+                     int64_t row_step) {
+  unsigned thr;
+  if (int rc = rows_drop_check("dropout_rows", rate, rng, row_step, &thr)) return rc;
+  if (dtype != SAE_DTYPE_BF16 && dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "dropout_rows: bad dtype %d", dtype);
+  if (M < 1 || C < 1 || ldx < C || ldy < C)
+    return fail(SAE_EINVAL, "dropout_rows: M %d, C %d, ldx %lld, ldy %lld", M, C, (long long)ldx, (long long)ldy);
+  if (!x || !y) return fail(SAE_EINVAL, "dropout_rows: x and y must be non-NULL");
+  DropRowsArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.y = y;
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.M = M;
+  a.C = C;
+  a.d = make_drop_rows(rng, stream_id, thr, row0, row_step);   // T = 0: every byte >= 0, inv = 1 -- a copy
+  const uintptr_t amask = (uintptr_t)(4 * elem_size(dtype) - 1);
+  a.vec = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && !((uintptr_t)x & amask) && !((uintptr_t)y & amask);
+  const long long total = (long long)M * ((C + 3) / 4);
+  const long long grid = std::min<long long>((total + 255) / 256, 16384);
+  return dtype == SAE_DTYPE_BF16
+             ? launch("dropout_rows", dropout_rows_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, a)
+             : launch("dropout_rows", dropout_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
+}
+
+int sae_dropout_rows_mask(void* stream, int32_t M, int32_t C, float rate, const uint64_t* rng, uint32_t stream_id,
+                          int64_t row0, int64_t row_step, uint8_t* keep) {
+  unsigned thr;
+  if (int rc = rows_drop_check("dropout_rows_mask", rate, rng, row_step, &thr)) return rc;
+  if (M < 1 || C < 1 || !keep) return fail(SAE_EINVAL, "dropout_rows_mask: M %d, C %d, keep %p", M, C, (void*)keep);
+  DropRowsArgs a;
+  memset(&a, 0, sizeof a);
+  a.keep = keep;
+  a.M = M;
+  a.C = C;
+  a.d = make_drop_rows(rng, stream_id, thr, row0, row_step);
+  return launch("dropout_rows_mask", dropout_rows_mask_kernel, ((long long)M * C + 255) / 256, dim3(256), 0,
+                (hipStream_t)stream, a);
+}
+
+int sae_layernorm_fwd_dropout(void* stream, int32_t M, int32_t C, const float* x, const void* delta, float* xout,
+                              const float* gamma, const float* beta, void* y, float* mean, float* rstd, float eps,
+                              float rate, const uint64_t* rng, uint32_t stream_id, int64_t row0, int64_t row_step) {
+  unsigned thr;
+  if (int rc = rows_drop_check("layernorm_fwd_dropout", rate, rng, row_step, &thr)) return rc;
+  if (!delta) return fail(SAE_EINVAL, "layernorm_fwd_dropout: delta is required");
+  if (thr == 0) return sae_layernorm_fwd(stream, M, C, x, delta, xout, gamma, beta, y, mean, rstd, eps);
+  const DropRows d = make_drop_rows(rng, stream_id, thr, row0, row_step);
+  return ln_fwd_impl(stream, M, C, x, delta, xout, gamma, beta, y, mean, rstd, eps, nullptr, nullptr, 1, &d);
+}
+
+int sae_layernorm_bwd_dropout(void* stream, int32_t M, int32_t C, const float* x, const float* mean,
+                              const float* rstd, const float* gamma, const void* dy, const float* dxin, float* dx,
+                              void* ddelta, float* dgamma, float* dbeta, void* workspace, float rate,
+                              const uint64_t* rng, uint32_t stream_id, int64_t row0, int64_t row_step) {
+  unsigned thr;
+  if (int rc = rows_drop_check("layernorm_bwd_dropout", rate, rng, row_step, &thr)) return rc;
+  if (thr == 0) return sae_layernorm_bwd(stream, M, C, x, mean, rstd, gamma, dy, dxin, dx, ddelta, dgamma, dbeta, workspace);
+  const DropRows d = make_drop_rows(rng, stream_id, thr, row0, row_step);
+  return ln_bwd_impl(stream, M, C, x, mean, rstd, gamma, dy, dxin, dx, ddelta, dgamma, dbeta, workspace, nullptr,
+                     nullptr, nullptr, 1, nullptr, &d);
+}
+
+int sae_tokens_fwd_dropout(void* stream, int32_t B, int32_t L, int32_t E, const void* tokens, const float* cls,
+                           const float* pos, float* x, float rate, const uint64_t* rng, uint32_t stream_id) {
+  unsigned thr;
+  if (int rc = rows_drop_check("tokens_fwd_dropout", rate, rng, 1, &thr)) return rc;
+  if (thr == 0) return sae_tokens_fwd(stream, B, L, E, tokens, cls, pos, x);
+  const DropRows d = make_drop_rows(rng, stream_id, thr, 0, 1);
+  return tokens_fwd_impl(stream, B, L, E, tokens, cls, pos, x, &d);
+}
+
+int sae_tokens_bwd_dropout(void* stream, int32_t B, int32_t L, int32_t E, const float* dx, void* dtokens, float* dcls,
+                           float* dpos, float rate, const uint64_t* rng, uint32_t stream_id) {
+  unsigned thr;
+  if (int rc = rows_drop_check("tokens_bwd_dropout", rate, rng, 1, &thr)) return rc;
+  if (thr == 0) return sae_tokens_bwd(stream, B, L, E, dx, dtokens, dcls, dpos);
+  const DropRows d = make_drop_rows(rng, stream_id, thr, 0, 1);
+  return tokens_bwd_impl(stream, B, L, E, dx, dtokens, dcls, dpos, &d);
 }
 
 int sae_smoothed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "weight_cast", "cast_weights", "clear_weight_cache", "gemm_dw", "set_weight_grad_stream", "join_weight_grad_stream", "layer_norm", "add_layer_norm", "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed", "relpos_bias", "rotary",
+__all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "weight_cast", "cast_weights", "clear_weight_cache", "gemm_dw", "set_weight_grad_stream", "join_weight_grad_stream", "layer_norm", "add_layer_norm", "dropout_rows", "dropout_rows_mask", "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed", "relpos_bias", "rotary",
            "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer"]
 
 
@@ -260,6 +260,63 @@ def _draw(dropout):
     if not 0.0 <= float(rate) < 1.0:
         raise ValueError(f"dropout rate {rate} is outside [0, 1)")
     return (float(rate), rng.state, rng.next_stream())
+
+
+# ------------------------------------------------------------------- hidden-state dropout
+def dropout_rows_mask(M: int, C: int, rate: float, rng: DropoutRng, stream_id: int, row0: int = 0,
+                      row_step: int = 1) -> torch.Tensor:
+    """uint8 ``keep[M, C]`` of the hidden-state dropout (``sae_dropout_rows_mask``): what
+    :func:`dropout_rows` and the ``dropout=`` forms of ``add_layer_norm``, ``cls_add_layer_norm``,
+    ``encoder_tokens`` and ``ff_block`` apply for rows ``row0 + i * row_step``."""
+    lib = L.load()
+    _require_gpu(rng.state)
+    keep = torch.empty((M, C), dtype=torch.uint8, device=rng.state.device)
+    L.check(lib.sae_dropout_rows_mask(_stream(keep), M, C, float(rate), _ptr(rng.state), int(stream_id), int(row0),
+                                      int(row_step), _ptr(keep)))
+    return keep
+
+
+def _dropout_rows_call(x2, y2, drop):
+    lib = L.load()
+    M, C = x2.shape
+    L.check(lib.sae_dropout_rows(_stream(x2), M, C, dtype_code(x2.dtype), _ptr(x2), x2.stride(0), _ptr(y2),
+                                 y2.stride(0), drop[0], _ptr(drop[1]), drop[2], 0, 1))
+
+
+class _DropoutRows(torch.autograd.Function):
+    """y = x * keep / pk over the rows of x viewed as [M, C] (C = the last dimension); the backward
+    is the same kernel on the gradient with the stream id the forward drew."""
+
+    @staticmethod
+    def forward(ctx, x, drop):
+        x2 = x.reshape(-1, x.shape[-1])
+        if x2.stride(1) != 1:
+            x2 = x2.contiguous()
+        y2 = torch.empty_like(x2, memory_format=torch.contiguous_format)
+        _dropout_rows_call(x2, y2, drop)
+        ctx.drop = drop
+        return y2.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        d2 = dy.reshape(-1, dy.shape[-1])
+        if d2.stride(1) != 1:
+            d2 = d2.contiguous()
+        dx = torch.empty_like(d2, memory_format=torch.contiguous_format)
+        _dropout_rows_call(d2, dx, ctx.drop)
+        return dx.view(dy.shape), None
+
+
+def dropout_rows(x: torch.Tensor, dropout=None) -> torch.Tensor:
+    """Hidden-state dropout ``x * keep / pk`` (``sae_dropout_rows``; bf16 or fp32) of ``x`` [.., C]
+    viewed as rows x C, with ``dropout = (rate, DropoutRng)``; ``None`` returns ``x``.  One stream id
+    is drawn per call.  The paths the fused ``dropout=`` forms do not take."""
+    if dropout is None:
+        return x
+    _require_gpu(x)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"dropout_rows: dtype {x.dtype} is not float32 / bfloat16")
+    return _DropoutRows.apply(x, _draw(dropout))
 
 
 def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None, drop=None):
@@ -1227,10 +1284,12 @@ def weight_cast(w: torch.Tensor, plain: bool = True, transposed: bool = True):
 
 
 def gemm_nt(a2: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = EPI_NONE,
-            aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+            aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, drop=None):
     """``epi(a2 @ bt^T (+ bias))`` through ``sae_gemm_nt``: a2 [M, K], bt [N, K] bf16.  Returns c,
     or (c, h) for the GELU epilogue (c = gelu(h), h = the bf16 pre-activation), or (c, g) for
-    EPI_GELU_GRAD (g = bf16(gelu'(h)), the aux of a later EPI_MUL_AUX call)."""
+    EPI_GELU_GRAD (g = bf16(gelu'(h)), the aux of a later EPI_MUL_AUX call).  ``drop`` (a drawn
+    ``(rate, state, stream_id)``, EPI_GELU_GRAD only): c and g times keep / pk of the hidden-state
+    dropout over [M, N] (``sae_gemm_nt_gelu_dropout``)."""
     lib = L.load()
     _require_gpu(a2, bt)
     M, K = a2.shape
@@ -1255,6 +1314,13 @@ def gemm_nt(a2: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = N
         aux = aux.contiguous()
     if bias is not None:
         bias = bias.float().contiguous()
+    if drop is not None:
+        if epilogue != EPI_GELU_GRAD:
+            raise ValueError("gemm_nt: dropout rides in the EPI_GELU_GRAD epilogue only")
+        L.check(lib.sae_gemm_nt_gelu_dropout(_stream(a2), M, N, K, _ptr(a2), a2.stride(0), _ptr(bt), bt.stride(0),
+                                             _ptr(bias), _ptr(c), c.stride(0), _ptr(c2), drop[0], _ptr(drop[1]),
+                                             drop[2]))
+        return c, c2
     L.check(lib.sae_gemm_nt(_stream(a2), M, N, K, _ptr(a2), a2.stride(0), _ptr(bt), bt.stride(0), _ptr(bias),
                             _ptr(c), c.stride(0), int(epilogue), _ptr(aux), aux.stride(0) if aux is not None else 0,
                             _ptr(c2)))
@@ -1268,15 +1334,15 @@ class _FFBlock(torch.autograd.Function):
     through ``sae_gemm_dw``."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, w1, b1):
+    def forward(ctx, x, w0, b0, w1, b1, drop=None):
         I, Hd = w0.shape
         x2 = x.to(torch.bfloat16).reshape(-1, I)
         if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
             x2 = x2.contiguous()
         w0p, w0t = _cast([w0], torch.bfloat16)
         w1p, w1t = _cast([w1], torch.bfloat16)
-        gg = FF_GELU_GRAD
-        a, h = gemm_nt(x2, w0t, b0, EPI_GELU_GRAD if gg else EPI_GELU)   # h: gelu'(pre-activation)
+        gg = FF_GELU_GRAD or drop is not None   # the hidden dropout rides in the saved gelu'(h)
+        a, h = gemm_nt(x2, w0t, b0, EPI_GELU_GRAD if gg else EPI_GELU, drop=drop)   # h: gelu'(pre-activation)
         y = gemm_nt(a, w1t, b1)                                   # Dense_1 forward
         ctx.save_for_backward(x2, h, a, w0p, w1p)
         ctx.gg = gg
@@ -1306,7 +1372,7 @@ class _FFBlock(torch.autograd.Function):
             torch.empty((Hd,), dtype=torch.float32, device=dev) if ctx.has_b[0] else None)
         gemm_dw(x2, dh, dw0, db0, offload=sw0 is not None and (sb0 is not None or not ctx.has_b[0]))
         ret = [None if sk is not None else g for sk, g in zip(ctx.sinks, (dw0, db0, dw1, db1))]
-        return (dx.view(ctx.xshape).to(ctx.xdtype), *ret)
+        return (dx.view(ctx.xshape).to(ctx.xdtype), *ret, None)
 
 
 FF_FUSED = True   # tools/ab_step.py flips this to A/B against the library GEMM + torch GELU path
@@ -1322,10 +1388,12 @@ def ff_block_ok(x: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor) -> bool:
 
 
 def ff_block(x: torch.Tensor, w0: torch.Tensor, b0: Optional[torch.Tensor], w1: torch.Tensor,
-             b1: Optional[torch.Tensor]) -> torch.Tensor:
-    """Flax FFBlock (ff.py:8-34, dropout 0) in bf16 with fp32 params: x [.., I] -> [.., O]."""
+             b1: Optional[torch.Tensor], dropout=None) -> torch.Tensor:
+    """Flax FFBlock (ff.py:8-34) in bf16 with fp32 params: x [.., I] -> [.., O].  ``dropout =
+    (rate, DropoutRng)``: the hidden dropout after the GELU (ff.py:30), inside Dense_0's GEMM
+    epilogue; the output dropout (ff.py:32) belongs to the caller's residual add."""
     _require_gpu(x, w0, w1)
-    return _FFBlock.apply(x, w0, b0, w1, b1)
+    return _FFBlock.apply(x, w0, b0, w1, b1, _draw(dropout))
 
 
 # ------------------------------------------------------------------ residual add + LayerNorm
@@ -1352,7 +1420,7 @@ def _bf16c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _ln_fwd(x, delta, gamma, beta, eps):
+def _ln_fwd(x, delta, gamma, beta, eps, drop=None, rows=(0, 1)):
     lib = L.load()
     x, gamma, beta = _f32c(x, "x"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
     if delta is not None:
@@ -1363,12 +1431,17 @@ def _ln_fwd(x, delta, gamma, beta, eps):
     mean = torch.empty(M, dtype=torch.float32, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
     xout = torch.empty_like(x) if delta is not None else None
+    if drop is not None:   # the addend dropped as it is added: mask rows rows[0] + i * rows[1]
+        L.check(lib.sae_layernorm_fwd_dropout(_stream(x), M, C, _ptr(x), _ptr(delta), _ptr(xout), _ptr(gamma),
+                                              _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), float(eps), drop[0],
+                                              _ptr(drop[1]), drop[2], int(rows[0]), int(rows[1])))
+        return xout, y, mean, rstd
     L.check(lib.sae_layernorm_fwd(_stream(x), M, C, _ptr(x), _ptr(delta), _ptr(xout), _ptr(gamma), _ptr(beta),
                                   _ptr(y), _ptr(mean), _ptr(rstd), float(eps)))
     return xout, y, mean, rstd
 
 
-def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None)):
+def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None), drop=None, rows=(0, 1)):
     lib = L.load()
     C = xs.shape[-1]
     M = xs.numel() // C
@@ -1381,6 +1454,11 @@ def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None)):
     ws = torch.empty(lib.sae_layernorm_bwd_workspace_bytes(M, C), dtype=torch.uint8, device=xs.device)
     if dxin is not None:
         dxin = _f32c(dxin, "dxin")
+    if drop is not None:   # ddelta = bf16(dx * keep / pk): the forward's mask
+        L.check(lib.sae_layernorm_bwd_dropout(_stream(xs), M, C, _ptr(xs), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                              _ptr(dy), _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db),
+                                              _ptr(ws), drop[0], _ptr(drop[1]), drop[2], int(rows[0]), int(rows[1])))
+        return dx, ddelta, dg, db
     L.check(lib.sae_layernorm_bwd(_stream(xs), M, C, _ptr(xs), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dy),
                                   _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db), _ptr(ws)))
     return dx, ddelta, dg, db
@@ -1409,10 +1487,10 @@ class _LayerNorm(torch.autograd.Function):
 
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, delta, gamma, beta, eps):
-        xout, y, mean, rstd = _ln_fwd(x, delta, gamma, beta, eps)
+    def forward(ctx, x, delta, gamma, beta, eps, drop=None):
+        xout, y, mean, rstd = _ln_fwd(x, delta, gamma, beta, eps, drop)
         ctx.save_for_backward(xout, mean, rstd, gamma)
-        ctx.delta_dtype = delta.dtype
+        ctx.delta_dtype, ctx.drop = delta.dtype, drop
         ctx.sinks = (_sink(gamma), _sink(beta))
         return xout, y
 
@@ -1422,8 +1500,8 @@ class _AddLayerNorm(torch.autograd.Function):
         xout, mean, rstd, gamma = ctx.saved_tensors
         if dy is None:
             dy = torch.zeros(xout.shape, dtype=torch.bfloat16, device=xout.device)
-        dx, ddelta, dg, db = _ln_bwd(xout, mean, rstd, gamma, dy, dxout, True, ctx.sinks)
-        return dx, ddelta.to(ctx.delta_dtype), _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None
+        dx, ddelta, dg, db = _ln_bwd(xout, mean, rstd, gamma, dy, dxout, True, ctx.sinks, ctx.drop)
+        return dx, ddelta.to(ctx.delta_dtype), _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None, None
 
 
 class _AddLayerNormScaled(torch.autograd.Function):
@@ -1497,11 +1575,13 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
 
 
 def add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                   eps: float = LN_EPS):
+                   eps: float = LN_EPS, dropout=None):
     """``x + delta`` (fp32 residual add, models/vit.py:24,31) and its LayerNorm in bf16, one kernel;
-    returns ``(x + delta, LN(x + delta))``."""
+    returns ``(x + delta, LN(x + delta))``.  ``dropout = (rate, DropoutRng)``: the hidden dropout of
+    the addend (the attention-output / FF-output dropout of vit.py:22,29) applied as it is added,
+    ``x + delta * keep / pk``."""
     _require_gpu(x, delta)
-    return _AddLayerNorm.apply(x, delta, gamma, beta, eps)
+    return _AddLayerNorm.apply(x, delta, gamma, beta, eps, _draw(dropout))
 
 
 # ------------------------------------------------------------------------------ training loss
@@ -1552,12 +1632,16 @@ class _EncoderTokens(torch.autograd.Function):
     multi-rank step registered them."""
 
     @staticmethod
-    def forward(ctx, tokens, cls, pos):
+    def forward(ctx, tokens, cls, pos, drop=None):
         lib = L.load()
         B, Lt, E = tokens.shape
         x = torch.empty((B, Lt + 1, E), dtype=torch.float32, device=tokens.device)
-        L.check(lib.sae_tokens_fwd(_stream(tokens), B, Lt, E, _ptr(tokens), _ptr(cls), _ptr(pos), _ptr(x)))
-        ctx.shape = (B, Lt, E)
+        if drop is not None:
+            L.check(lib.sae_tokens_fwd_dropout(_stream(tokens), B, Lt, E, _ptr(tokens), _ptr(cls), _ptr(pos), _ptr(x),
+                                               drop[0], _ptr(drop[1]), drop[2]))
+        else:
+            L.check(lib.sae_tokens_fwd(_stream(tokens), B, Lt, E, _ptr(tokens), _ptr(cls), _ptr(pos), _ptr(x)))
+        ctx.shape, ctx.drop = (B, Lt, E), drop
         ctx.sinks = (_sink(cls), _sink(pos))
         ctx.meta = (cls.shape, pos.shape)
         return x
@@ -1572,8 +1656,12 @@ class _EncoderTokens(torch.autograd.Function):
         scls, spos = ctx.sinks
         dcls = _claim(scls) if scls is not None else torch.empty(ctx.meta[0], dtype=torch.float32, device=dx.device)
         dpos = _claim(spos) if spos is not None else torch.empty(ctx.meta[1], dtype=torch.float32, device=dx.device)
-        L.check(lib.sae_tokens_bwd(_stream(dx), B, Lt, E, _ptr(dx), _ptr(dtok), _ptr(dcls), _ptr(dpos)))
-        return dtok, _unsunk(dcls, scls), _unsunk(dpos, spos)
+        if ctx.drop is not None:
+            L.check(lib.sae_tokens_bwd_dropout(_stream(dx), B, Lt, E, _ptr(dx), _ptr(dtok), _ptr(dcls), _ptr(dpos),
+                                               ctx.drop[0], _ptr(ctx.drop[1]), ctx.drop[2]))
+        else:
+            L.check(lib.sae_tokens_bwd(_stream(dx), B, Lt, E, _ptr(dx), _ptr(dtok), _ptr(dcls), _ptr(dpos)))
+        return dtok, _unsunk(dcls, scls), _unsunk(dpos, spos), None
 
 
 def encoder_tokens_ok(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor) -> bool:
@@ -1587,13 +1675,14 @@ def encoder_tokens_ok(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor
             and pos.data_ptr() % 16 == 0)
 
 
-def encoder_tokens(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
-    """fp32 [B, L+1, E] encoder input = concat(cls, float(tokens)) + pos (see _EncoderTokens)."""
+def encoder_tokens(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, dropout=None) -> torch.Tensor:
+    """fp32 [B, L+1, E] encoder input = concat(cls, float(tokens)) + pos (see _EncoderTokens).
+    ``dropout = (rate, DropoutRng)``: the encoder-input dropout of vit.py:47 in the same pass."""
     _require_gpu(tokens, cls, pos)
     if not encoder_tokens_ok(tokens, cls, pos):
         raise ValueError("encoder_tokens: needs bf16 contiguous tokens [B, L, E] (E % 4 == 0) and fp32 "
                          "contiguous cls [E] / pos [L+1, E]")
-    return _EncoderTokens.apply(tokens, cls, pos)
+    return _EncoderTokens.apply(tokens, cls, pos, _draw(dropout))
 
 
 class _LayerNormPass(torch.autograd.Function):
@@ -1631,10 +1720,12 @@ class _ClsAddLayerNorm(torch.autograd.Function):
     dx (fp32) and ddelta (bf16); the other rows take no gradient from here."""
 
     @staticmethod
-    def forward(ctx, x, delta, gamma, beta, eps):
-        xout, y, mean, rstd = _ln_fwd(x[:, 0], delta[:, 0], gamma, beta, eps)
+    def forward(ctx, x, delta, gamma, beta, eps, drop=None):
+        # dropout: the class rows are rows b * N of the [B * N, E] tensor -- the full form's mask
+        ctx.rows = (0, x.shape[1])
+        xout, y, mean, rstd = _ln_fwd(x[:, 0], delta[:, 0], gamma, beta, eps, drop, ctx.rows)
         ctx.save_for_backward(xout, mean, rstd, gamma)
-        ctx.meta = (x.shape, delta.dtype)
+        ctx.meta, ctx.drop = (x.shape, delta.dtype), drop
         ctx.sinks = (_sink(gamma), _sink(beta))
         return y
 
@@ -1643,16 +1734,17 @@ class _ClsAddLayerNorm(torch.autograd.Function):
     def backward(ctx, dy):
         xout, mean, rstd, gamma = ctx.saved_tensors
         shape, ddt = ctx.meta
-        dxc, ddc, dg, db = _ln_bwd(xout, mean, rstd, gamma, dy, None, True, ctx.sinks)
+        dxc, ddc, dg, db = _ln_bwd(xout, mean, rstd, gamma, dy, None, True, ctx.sinks, ctx.drop, ctx.rows)
         dx = torch.zeros(shape, dtype=torch.float32, device=dxc.device)
         dx[:, 0] = dxc
         dd = torch.zeros(shape, dtype=ddt, device=dxc.device)
         dd[:, 0] = ddc
-        return dx, dd, _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None
+        return dx, dd, _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None, None
 
 
 def cls_add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                       eps: float = LN_EPS) -> torch.Tensor:
-    """bf16 LayerNorm(x[:, 0] + delta[:, 0]) of the [B, N, E] residual stream -- see _ClsAddLayerNorm."""
+                       eps: float = LN_EPS, dropout=None) -> torch.Tensor:
+    """bf16 LayerNorm(x[:, 0] + delta[:, 0]) of the [B, N, E] residual stream -- see _ClsAddLayerNorm.
+    ``dropout``: as :func:`add_layer_norm`, with the class rows' slice of the full tensor's mask."""
     _require_gpu(x, delta, gamma, beta)
-    return _ClsAddLayerNorm.apply(x, delta, gamma, beta, eps)
+    return _ClsAddLayerNorm.apply(x, delta, gamma, beta, eps, _draw(dropout))

@@ -395,12 +395,13 @@ class TrainStep:
             except (RuntimeError, TypeError):
                 self.opt = torch.optim.AdamW(params, foreach=True, **kw)
         self.smoothing = label_smoothing
-        # attention-probability dropout (attn_dropout_rate > 0 on any module): the first operation
+        # dropout (attn_dropout_rate > 0 or dropout_rate > 0 on any module): the first operation
         # of each step bumps the device offset of the dropout state (ops.DropoutRng.advance), so
         # every step -- every replay of the captured graph included -- draws fresh masks.  With
         # rate 0 everywhere the step launches nothing for it.
         self._drop_rng = None
-        if on_gpu and any(getattr(m, "attn_dropout_rate", 0.0) > 0.0 for m in model.modules()):
+        if on_gpu and any(getattr(m, "attn_dropout_rate", 0.0) > 0.0 or getattr(m, "dropout_rate", 0.0) > 0.0
+                          for m in model.modules()):
             from . import ops
             self._drop_rng = ops.dropout_rng(params[0].device)
 

@@ -14,6 +14,15 @@ The attention is ``layers.SelfAttentionBlock`` (fused HIP kernels).  Around it (
 HIP split-token weight/bias gradients), and with a bf16 compute dtype every residual add is fused
 with the LayerNorm that follows it (``ops.add_layer_norm``, HIP) and the FF block runs as
 ``ops.ff_block`` (HIP GEMMs with the tanh-GELU and its derivative fused into their epilogues).
+
+``dropout_rate`` (vit.py:12,39,68) reaches four places per training forward, each drawing one stream id
+of the device's ``ops.DropoutRng`` in this order: the encoder input after the position embedding
+(vit.py:47); then per block the attention probabilities (``attn_dropout_rate``, inside the attention
+kernels), the attention output (attention.py ``out_dropout_rate``), the FF hidden activation after
+the GELU (ff.py:30) and the FF output (ff.py:32).  In the fused bf16 encoder none of them is a pass
+of its own: the input dropout rides in ``ops.encoder_tokens``, the hidden one in the GELU GEMM's
+epilogue, the two output ones in the ``ops.add_layer_norm`` that follows; every other path applies
+``ops.dropout_rows`` at the same places with the same ids, so one seed gives one set of masks.
 """
 from __future__ import annotations
 
@@ -57,39 +66,56 @@ class LayerNorm(nn.Module):
         return F.layer_norm(x.float(), (x.shape[-1],), self.scale, self.bias, 1e-6).to(dtype)
 
 
-class FFBlock(nn.Module):
-    """ff.py:8-34 (expand_ratio, Dense -> GELU -> Dense, dropout 0)."""
+def _hidden_dropout(rate: float, is_training: bool, device):
+    """``(rate, DropoutRng)`` for the ops' ``dropout=`` argument, or None (inference, rate 0)."""
+    return (rate, ops.dropout_rng(device)) if is_training and rate > 0.0 else None
 
-    def __init__(self, dim, expand_ratio=4, device=None):
+
+class FFBlock(nn.Module):
+    """ff.py:8-34 (expand_ratio, Dense -> GELU -> Dropout -> Dense -> Dropout)."""
+
+    def __init__(self, dim, expand_ratio=4, device=None, dropout_rate: float = 0.0):
         super().__init__()
         hid = max(1, int(expand_ratio * dim))
+        self.dropout_rate = dropout_rate
         self.Dense_0 = Dense(dim, hid, device=device)
         self.Dense_1 = Dense(hid, dim, device=device)
 
-    def forward(self, x, dtype):
+    def forward(self, x, dtype, is_training: bool = False, out_dropout: bool = True):
+        """``out_dropout=False``: the caller applies the output dropout (ff.py:32) itself, inside the
+        residual add that follows (``ops.add_layer_norm(dropout=...)``)."""
         d0, d1 = self.Dense_0, self.Dense_1
+        drop = _hidden_dropout(self.dropout_rate, is_training, x.device)
         if dtype == torch.bfloat16 and ops.ff_block_ok(x, d0.kernel, d1.kernel):
-            # GELU fused into Dense_0's GEMM epilogue, its derivative into Dense_1's dX GEMM
-            return ops.ff_block(x, d0.kernel, d0.bias, d1.kernel, d1.bias)
-        return d1(F.gelu(d0(x, dtype), approximate="tanh"), dtype)
+            # GELU (and the hidden dropout) fused into Dense_0's GEMM epilogue, its derivative into
+            # Dense_1's dX GEMM
+            y = ops.ff_block(x, d0.kernel, d0.bias, d1.kernel, d1.bias, dropout=drop)
+        else:
+            y = d1(ops.dropout_rows(F.gelu(d0(x, dtype), approximate="tanh"), drop), dtype)
+        return ops.dropout_rows(y, drop) if out_dropout else y
 
 
 class EncoderBlock(nn.Module):
     """vit.py:9-32."""
 
-    def __init__(self, dim, num_heads, expand_ratio, dtype, device=None, attn_dropout_rate: float = 0.0):
+    def __init__(self, dim, num_heads, expand_ratio, dtype, device=None, attn_dropout_rate: float = 0.0,
+                 dropout_rate: float = 0.0):
         super().__init__()
         self.dtype = dtype
+        self.dropout_rate = dropout_rate
         self.LayerNorm_0 = LayerNorm(dim, device)
+        # out_dropout_rate stays 0: the block owns the attention-output dropout (vit.py:22), so that
+        # the fused encoder can apply it inside the residual add
         self.SelfAttentionBlock_0 = SelfAttentionBlock(num_heads=num_heads, attn_dropout_rate=attn_dropout_rate,
                                                        dtype=dtype, in_ch=dim, device=device)
         self.LayerNorm_1 = LayerNorm(dim, device)
-        self.FFBlock_0 = FFBlock(dim, expand_ratio, device)
+        self.FFBlock_0 = FFBlock(dim, expand_ratio, device, dropout_rate)
 
     def forward(self, inputs, is_training):
         x = self.SelfAttentionBlock_0(self.LayerNorm_0(inputs, self.dtype), is_training=is_training)
+        x = ops.dropout_rows(x, _hidden_dropout(self.dropout_rate, is_training, x.device))
         x = x + inputs
-        y = self.FFBlock_0(self.LayerNorm_1(x, self.dtype), self.dtype)
+        y = self.FFBlock_0(self.LayerNorm_1(x, self.dtype), self.dtype, is_training)
         return x + y
 
 
@@ -107,22 +133,27 @@ class Encoder(nn.Module):
     """vit.py:35-58 (AddAbsPosEmbed_0 + EncoderBlock_i + LayerNorm_0)."""
 
     def __init__(self, num_tokens, dim, num_layers, num_heads, expand_ratio, dtype, device=None,
-                 attn_dropout_rate: float = 0.0):
+                 attn_dropout_rate: float = 0.0, dropout_rate: float = 0.0):
         super().__init__()
         self.dtype = dtype
+        self.dropout_rate = dropout_rate
         self.AddAbsPosEmbed_0 = nn.Module()
         self.AddAbsPosEmbed_0.pos_embed = nn.Parameter(torch.randn(1, num_tokens, dim, device=device) * 0.02)
         for i in range(num_layers):
             setattr(self, f"EncoderBlock_{i}", EncoderBlock(dim, num_heads, expand_ratio, dtype, device,
-                                                            attn_dropout_rate))
+                                                            attn_dropout_rate, dropout_rate))
         self.num_layers = num_layers
         self.LayerNorm_0 = LayerNorm(dim, device)
 
     def forward(self, inputs, is_training, pos_added: bool = False, cls_only: bool = False):
-        """``pos_added``: ``inputs`` already hold the position embedding (ops.encoder_tokens).
+        """``pos_added``: ``inputs`` already hold the position embedding and, when training with
+        ``dropout_rate > 0``, the input dropout of vit.py:47 (ops.encoder_tokens).
         ``cls_only``: return only token 0 of the normalised output, [B, E] (what ViT's head reads,
         vit.py:95): the final residual add and LayerNorm (row-wise) then run on those rows only."""
-        x = inputs if pos_added else inputs.float() + self.AddAbsPosEmbed_0.pos_embed
+        x = inputs
+        if not pos_added:
+            x = inputs.float() + self.AddAbsPosEmbed_0.pos_embed
+            x = ops.dropout_rows(x, _hidden_dropout(self.dropout_rate, is_training, x.device))
         blocks = [getattr(self, f"EncoderBlock_{i}") for i in range(self.num_layers)]
         if self.dtype == torch.bfloat16 and blocks and ops.layer_norm_ok(x):
             # Same math as vit.py:19-31,57, with every residual add fused into the LayerNorm that
@@ -133,16 +164,20 @@ class Encoder(nn.Module):
                 # (x, h): the residual gradient is added inside the LayerNorm backward kernel
                 x, h = ops.layer_norm_pass(x, blocks[0].LayerNorm_0.scale, blocks[0].LayerNorm_0.bias)
                 for i, blk in enumerate(blocks):
+                    # the attention-output and FF-output dropouts ride in the residual add that follows
+                    drop = _hidden_dropout(blk.dropout_rate, is_training, x.device)
                     a = blk.SelfAttentionBlock_0(h, is_training=is_training)
-                    x, h = ops.add_layer_norm(x, a, blk.LayerNorm_1.scale, blk.LayerNorm_1.bias)
-                    f = blk.FFBlock_0(h, self.dtype)
+                    x, h = ops.add_layer_norm(x, a, blk.LayerNorm_1.scale, blk.LayerNorm_1.bias, dropout=drop)
+                    f = blk.FFBlock_0(h, self.dtype, is_training, out_dropout=False)
                     if i + 1 < len(blocks):
                         nxt = blocks[i + 1].LayerNorm_0
-                        x, h = ops.add_layer_norm(x, f, nxt.scale, nxt.bias)
+                        x, h = ops.add_layer_norm(x, f, nxt.scale, nxt.bias, dropout=drop)
                     elif cls_only:
-                        h = ops.cls_add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias)
+                        h = ops.cls_add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias,
+                                                   dropout=drop)
                     else:
-                        x, h = ops.add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias)
+                        x, h = ops.add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias,
+                                                  dropout=drop)
             finally:
                 ops.clear_weight_cache()
             return h
@@ -175,16 +210,19 @@ class ViT(nn.Module):
 
     def __init__(self, num_classes: int, num_layers: int, num_heads: int, embed_dim: int,
                  patch_shape: Tuple[int, int], img_size: int = 224, expand_ratio: float = 4,
-                 dtype: torch.dtype = torch.float32, device=None, attn_dropout_rate: float = 0.0):
+                 dtype: torch.dtype = torch.float32, device=None, attn_dropout_rate: float = 0.0,
+                 dropout_rate: float = 0.0):
         super().__init__()
         assert embed_dim % num_heads == 0
         self.patch_shape, self.dtype, self.embed_dim = tuple(patch_shape), dtype, embed_dim
+        self.dropout_rate = dropout_rate
         ph, pw = self.patch_shape
         self.PatchEmbedBlock_0 = nn.Module()
         self.PatchEmbedBlock_0.Dense_0 = Dense(ph * pw * 3, embed_dim, use_bias=False, device=device)
         self.cls = nn.Parameter(torch.zeros(1, 1, embed_dim, device=device))
         n = (img_size // ph) * (img_size // pw) + 1
-        self.Encoder_0 = Encoder(n, embed_dim, num_layers, num_heads, expand_ratio, dtype, device, attn_dropout_rate)
+        self.Encoder_0 = Encoder(n, embed_dim, num_layers, num_heads, expand_ratio, dtype, device, attn_dropout_rate,
+                                 dropout_rate)
         self.Dense_0 = Dense(embed_dim, num_classes, zero_init=True, device=device)
 
     def cast_groups(self):
@@ -203,8 +241,10 @@ class ViT(nn.Module):
         b = x.shape[0]
         pos = self.Encoder_0.AddAbsPosEmbed_0.pos_embed
         if self.dtype == torch.bfloat16 and ops.encoder_tokens_ok(x, self.cls, pos):
-            # concat(cls, tokens) + pos_embed into the fp32 residual stream in one pass
-            x = self.Encoder_0(ops.encoder_tokens(x, self.cls, pos), is_training, pos_added=True, cls_only=True)
+            # concat(cls, tokens) + pos_embed (and the input dropout) into the fp32 residual stream in one pass
+            drop = _hidden_dropout(self.dropout_rate, is_training, x.device)
+            x = self.Encoder_0(ops.encoder_tokens(x, self.cls, pos, dropout=drop), is_training, pos_added=True,
+                               cls_only=True)
         else:
             x = torch.cat([self.cls.expand(b, 1, self.embed_dim), x.float()], dim=1)   # fp32 (promotion)
             x = self.Encoder_0(x, is_training, cls_only=True)
@@ -223,13 +263,14 @@ MODEL_CONFIGS = {
 
 
 def create_model(model_name: str, num_classes: int = 1000, dtype: torch.dtype = torch.float32,
-                 img_size: int = 224, device=None, attn_dropout_rate: float = 0.0) -> ViT:
+                 img_size: int = 224, device=None, attn_dropout_rate: float = 0.0, dropout_rate: float = 0.0) -> ViT:
     """``create_model`` (models/create_model.py:6-215) for the ViT/DeiT family."""
     if model_name not in MODEL_CONFIGS:
         raise ValueError(f"unknown model {model_name!r}; ViT/DeiT family: {sorted(MODEL_CONFIGS)}")
     L, Hh, C, p = MODEL_CONFIGS[model_name]
     return ViT(num_classes=num_classes, num_layers=L, num_heads=Hh, embed_dim=C, patch_shape=(p, p),
-               img_size=img_size, dtype=dtype, device=device, attn_dropout_rate=attn_dropout_rate)
+               img_size=img_size, dtype=dtype, device=device, attn_dropout_rate=attn_dropout_rate,
+               dropout_rate=dropout_rate)
 
 
 def vit_flops_per_image(model_name: str, img_size: int = 224, num_classes: int = 1000) -> float:
