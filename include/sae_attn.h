@@ -226,6 +226,25 @@ int sae_th_attn_bwd_rotary(void* stream, const sae_attn_desc* desc, const void* 
                            const void* dout, const float* sin_tab, const float* cos_tab, void* dq,
                            void* dk, void* dv, float* dth1, float* dth2, void* workspace);
 
+/* Host-only queries (no device needed, no HIP call): which kernels the attention /
+   talking-heads entry point of that pass and form runs for this descriptor.  `aligned` stands for
+   "every tensor pointer of the call is 16-byte aligned"; the stride half of the vector-access
+   condition is read from the descriptor.  SAE_FORM_DROPOUT means a rate that drops something
+   (T > 0; T = 0 is the plain form); talking heads has no dropout form.  Returns the route's name --
+   the launched kernel instances in launch order, joined by '+' -- or NULL where the entry point
+   would refuse the call, with the reason in sae_last_error.  The string lives until the next call
+   into the library on this thread, as sae_last_error's does.  The names are the rows of the
+   instance tables in csrc/attn.hip, csrc/bwd2_run.h and csrc/th.hip: informative (logs, tests),
+   NOT part of the ABI -- a new kernel changes them without a new SAE_ABI_VERSION. */
+#define SAE_PASS_FWD 0
+#define SAE_PASS_BWD 1
+#define SAE_FORM_PLAIN 0
+#define SAE_FORM_ROTARY 1
+#define SAE_FORM_DROPOUT 2
+const char* sae_attn_route(const sae_attn_desc* desc, int32_t pass, int32_t form, int32_t aligned);
+const char* sae_th_attn_route(const sae_attn_desc* desc, int32_t pass, int32_t form,
+                              int32_t aligned);
+
 /* Weight / bias gradients of a projection on the path (the Dense / DenseGeneral kernels of
    attention.py:29-37,60-63 and ff.py:8-34, whose JAX autodiff computes them):
      dw[i][j] (+)= sum_m x[m][i] * dy[m][j]      dw fp32 [I][J] (row stride ldw)

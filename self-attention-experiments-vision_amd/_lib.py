@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("SAE_ATTN_LIB") or os.path.join(_PKG_DIR, "libsae_attn
 SAE_OK, SAE_EINVAL, SAE_EUNSUPPORTED, SAE_EHIP = 0, -1, -2, -3
 SAE_DTYPE_F32, SAE_DTYPE_BF16 = 0, 1
 SAE_FLAG_RELPOS = 1
+SAE_PASS_FWD, SAE_PASS_BWD = 0, 1
+SAE_FORM_PLAIN, SAE_FORM_ROTARY, SAE_FORM_DROPOUT = 0, 1, 2
 SAE_TH_MAX_HEADS = 16
 SAE_TH_MAX_HEAD_DIM = 64
 ABI_VERSION = 1
@@ -79,6 +81,8 @@ _PROTOS = [
     ("sae_attn_bwd_rotary", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 12),
     ("sae_th_attn_fwd_rotary", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 9),
     ("sae_th_attn_bwd_rotary", _i32, [_vp, ctypes.POINTER(SaeAttnDesc)] + [_vp] * 15),
+    ("sae_attn_route", ctypes.c_char_p, [ctypes.POINTER(SaeAttnDesc), _i32, _i32, _i32]),
+    ("sae_th_attn_route", ctypes.c_char_p, [ctypes.POINTER(SaeAttnDesc), _i32, _i32, _i32]),
     ("sae_gemm_dw_workspace_bytes", _sz, [_i32, _i32, _i32]),
     ("sae_gemm_dw", _i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _vp]),
     ("sae_gemm_dw_blocked", _i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),

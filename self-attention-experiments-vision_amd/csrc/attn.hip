@@ -53,74 +53,96 @@ void fill_args(AttnArgs& a, const sae_attn_desc* d) {
   }
 }
 
-// ---------------------------------------------------------------- template dispatch helpers
-template <template <typename, int, bool, bool> class L, typename... Args>
-int dispatch(int dtype, int dp, bool vec, bool rel, Args&&... args) {
-#define SAE_CASE(T, DPV)                                                            \
-  if (dp == DPV) {                                                                  \
-    if (vec) return rel ? L<T, DPV, true, true>::run(args...) : L<T, DPV, true, false>::run(args...); \
-    return rel ? L<T, DPV, false, true>::run(args...) : L<T, DPV, false, false>::run(args...);        \
+// ------------------------------------------------------------------------- v1 launchers
+// The v1 kernels (attn_kernels.h) cover the whole envelope: fp32, unaligned strides or head_dim,
+// relative logits on grids up to 64 x 64, dropout (REL && DROP is never instantiated).
+struct V1 {
+  int dtype, dp;
+  bool vec, rel, drop;
+};
+
+int rel_lds_floats(const AttnArgs& a) { return a.rel_h ? 32 * (a.rel_h + a.rel_w + 1) : 0; }
+
+template <typename T, int DP, bool VEC, bool REL, bool DROP> struct FwdL {
+  static int run(hipStream_t st, const AttnArgs& a) {
+    const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
+    const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK) + (REL ? 4 * rel_lds_floats(a) * sizeof(float) : 0);
+    return launch(DROP ? "attn_fwd_drop" : "attn_fwd", attn_fwd_kernel<T, DP, VEC, REL, DROP>, grid, dim3(256), lds, st,
+                  a);
   }
-  if (dtype == SAE_DTYPE_BF16) {
+};
+
+template <typename T, int DP, bool VEC, bool REL, bool DROP> struct BwdL {
+  static int run(hipStream_t st, const AttnArgs& a) {
+    {  // dQ (+ delta) first: it publishes delta for the dK/dV pass
+      const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
+      const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK) + (REL ? 8 * rel_lds_floats(a) * sizeof(float) : 0);
+      if (int rc = launch(DROP ? "attn_bwd_dq_drop" : "attn_bwd_dq", attn_bwd_dq_kernel<T, DP, VEC, REL, DROP>, grid,
+                          dim3(256), lds, st, a))
+        return rc;
+    }
+    const long long grid = (long long)((a.Nk + kBKV - 1) / kBKV) * a.H * a.B;
+    const size_t lds = nbuf<T, DP>() * (2 * Img<T, DP>::bytes(kBQT) + 2 * kBQT * sizeof(float) +
+                                        (REL ? (size_t)kBQT * (a.rel_h + a.rel_w + 1) * sizeof(float) : 0));
+    return launch(DROP ? "attn_bwd_dkdv_drop" : "attn_bwd_dkdv", attn_bwd_dkdv_kernel<T, DP, VEC, REL, DROP>, grid,
+                  dim3(256), lds, st, a);
+  }
+};
+
+template <template <typename, int, bool, bool, bool> class L, typename T, int DP, bool VEC>
+int v1_run(const V1& v, hipStream_t st, const AttnArgs& a) {
+  if (v.drop) return L<T, DP, VEC, false, true>::run(st, a);
+  return v.rel ? L<T, DP, VEC, true, false>::run(st, a) : L<T, DP, VEC, false, false>::run(st, a);
+}
+
+template <template <typename, int, bool, bool, bool> class L>
+int dispatch(const V1& v, hipStream_t st, const AttnArgs& a) {
+#define SAE_CASE(T, DPV) \
+  if (v.dp == DPV) return v.vec ? v1_run<L, T, DPV, true>(v, st, a) : v1_run<L, T, DPV, false>(v, st, a);
+  if (v.dtype == SAE_DTYPE_BF16) {
     SAE_CASE(__bf16, 32) SAE_CASE(__bf16, 64) SAE_CASE(__bf16, 128)
   } else {
     SAE_CASE(float, 32) SAE_CASE(float, 64) SAE_CASE(float, 128)
   }
 #undef SAE_CASE
-  return fail(SAE_EUNSUPPORTED, "no kernel instance for dtype %d dp %d", dtype, dp);
+  return fail(SAE_EUNSUPPORTED, "no kernel instance for dtype %d dp %d", v.dtype, v.dp);
 }
 
-int rel_lds_floats(const AttnArgs& a) { return a.rel_h ? 32 * (a.rel_h + a.rel_w + 1) : 0; }
-
-template <typename T, int DP, bool VEC, bool REL> struct FwdL {
-  static int run(hipStream_t st, const AttnArgs& a) {
-    const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
-    const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK) + (REL ? 4 * rel_lds_floats(a) * sizeof(float) : 0);
-    return launch("attn_fwd", attn_fwd_kernel<T, DP, VEC, REL>, grid, dim3(256), lds, st, a);
-  }
-};
-
-template <typename T, int DP, bool VEC, bool REL> struct BwdL {
-  static int run(hipStream_t st, const AttnArgs& a) {
-    {  // dQ (+ delta) first: it publishes delta for the dK/dV pass
-      const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
-      const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK) + (REL ? 8 * rel_lds_floats(a) * sizeof(float) : 0);
-      if (int rc = launch("attn_bwd_dq", attn_bwd_dq_kernel<T, DP, VEC, REL>, grid, dim3(256), lds, st, a)) return rc;
-    }
-    const long long grid = (long long)((a.Nk + kBKV - 1) / kBKV) * a.H * a.B;
-    const size_t lds = nbuf<T, DP>() * (2 * Img<T, DP>::bytes(kBQT) + 2 * kBQT * sizeof(float) +
-                                        (REL ? (size_t)kBQT * (a.rel_h + a.rel_w + 1) * sizeof(float) : 0));
-    return launch("attn_bwd_dkdv", attn_bwd_dkdv_kernel<T, DP, VEC, REL>, grid, dim3(256), lds, st, a);
-  }
-};
-
+// ------------------------------------------------------------------- lean kernel launchers
 // lean bf16 forward (fwd2.h): NW waves x 32 query rows per workgroup
-template <int DP, int NW, int MINW, bool LSUM, bool ROT = false, int NSU = DP / 16, bool REL = false,
-          bool FIX = false, bool DROP = false>
+template <int DP, int NW, int MINW, bool LSUM, bool ROT, int NSU, bool REL, bool FIX, bool DROP>
 int fwd2_run(hipStream_t st, const AttnArgs& a) {
   const long long grid = (long long)((a.Nq + 32 * NW - 1) / (32 * NW)) * a.H * a.B;
   const size_t lds = 4 * (size_t)F2<DP>::TILE + (REL ? 2 * kRelImg : 0);
   return launch("attn_fwd2", attn_fwd2_kernel<DP, NW, MINW, LSUM, ROT, NSU, REL, FIX, DROP>, grid, dim3(64 * NW), lds, st, a);
 }
 
-// BoTNet relative logits on the lean bf16 kernels: the table columns (Hs + Ws) fit the two extra
-// score k-steps; larger grids (up to 64 x 64) and fp32 take the v1 kernels
-bool rel_lean(const AttnArgs& a) { return a.rel_h + a.rel_w <= kRelCols; }
+// single-pass bf16 backward (bwd3.h): one workgroup per (batch, head) holding all Nk <= 256 keys
+// (8 waves x 32 keys, two waves per SIMD); longer key ranges take the two-pass bwd2
+constexpr int kB3Keys = 256;
 
-// single query row (CaiT class attention, CeiT LCA): the K/V stream kernels of cls.h
+template <int DP, int NW, int KPW, bool ROT, int NSU, bool DROP>
+int bwd3_run(hipStream_t st, const AttnArgs& a) {
+  using C = B3<DP, NW, KPW>;
+  static_assert(C::BK == kB3Keys, "bwd3 dispatch assumes 256-key blocks");
+  if (a.Nk > C::BK) return fail(SAE_EINVAL, "bwd3: %d keys > %d", a.Nk, C::BK);
+  return launch("attn_bwd3", attn_bwd3_kernel<DP, NW, KPW, ROT, NSU, DROP>, (long long)a.H * a.B, dim3(64 * NW), C::LDS, st,
+                a);
+}
+
+// single query row (CaiT class attention, CeiT LCA): the K/V stream kernels of cls.h, NCH 64-wide
+// head_dim chunks per row
 constexpr int kClsMaxKeys = 1 << 20;
-bool cls_ok(const sae_attn_desc* d) {
-  return d->seq_q == 1 && d->seq_k <= kClsMaxKeys && d->head_dim <= 128 && d->dtype == SAE_DTYPE_BF16 &&
-         !(d->flags & SAE_FLAG_RELPOS);
-}
-template <bool BWD> int cls_run(hipStream_t st, const AttnArgs& a) {
-  const bool two = a.D > 64;
-  const size_t lds = two ? cls_lds_bytes<2>() : cls_lds_bytes<1>();
-  void (*const fn)(AttnArgs) = BWD ? (two ? attn_cls_bwd_kernel<2> : attn_cls_bwd_kernel<1>)
-                                   : (two ? attn_cls_fwd_kernel<2> : attn_cls_fwd_kernel<1>);
-  return launch(BWD ? "attn_cls_bwd" : "attn_cls_fwd", fn, (long long)a.B * a.H, dim3(256), lds, st, a);
+template <bool BWD, int NCH> int cls_run(hipStream_t st, const AttnArgs& a) {
+  return launch(BWD ? "attn_cls_bwd" : "attn_cls_fwd", BWD ? attn_cls_bwd_kernel<NCH> : attn_cls_fwd_kernel<NCH>,
+                (long long)a.B * a.H, dim3(256), cls_lds_bytes<NCH>(), st, a);
 }
 
+// ------------------------------------------------------------------------ instance tables
+// Every instance of the lean bf16 kernels this unit holds is ONE row here (the two-pass backward's
+// rows are in bwd2_run.h): the template parameters are written once, under their names, and every
+// launch refers to the row's name.  A new instance is a new row, never a tuple at a call site.
+//
 // The lean forward's variant per padded head dim:
 //   DP <= 64: three waves per SIMD, row sum on the VALU, running max fixed by the first tile (FIX,
 //             with the tracking sweep as the in-kernel fallback): 23.2 vs 24.6 us at DeiT-S, 95.4 vs
@@ -130,37 +152,218 @@ template <bool BWD> int cls_run(hipStream_t st, const AttnArgs& a) {
 //             to the standalone rotary pass + this forward (tests/test_gpu_rotary.py).
 //   DP 128:   two waves per SIMD, row sum on the MFMA (the VALU row sum is 2x slower there,
 //             profiles/r01_attn_fwd_f0_vs_f6_interleaved_v13.txt).
-template <int DP, bool ROT = false> int fwd2_dispatch(hipStream_t st, const AttnArgs& a) {
-  if constexpr (DP <= 64) {
-    if (!ROT && DP == 64 && a.D <= 48) return fwd2_run<DP, 4, 3, false, false, 3, false, true>(st, a);
-    return fwd2_run<DP, 4, 3, false, ROT, DP / 16, false, true>(st, a);
-  } else {
-    return fwd2_run<DP, 4, 2, true, ROT>(st, a);
+//   REL:      BoTNet relative logits, two waves per SIMD, row sum on the MFMA.
+//   DROP:     the DP <= 64 variant with the dropped P zeroed; at DP 64 the Philox state does not fit
+//             three waves per SIMD (5 / 16 VGPRs spilled): two there.
+//  row name         DP   NW MINW LSUM   ROT    NSU REL    FIX    DROP
+#define SAE_FWD2_TABLE(X)                                              \
+  X(fwd2_d32,        32,  4, 3,   false, false, 2,  false, true,  false) \
+  X(fwd2_d64_k3,     64,  4, 3,   false, false, 3,  false, true,  false) \
+  X(fwd2_d64,        64,  4, 3,   false, false, 4,  false, true,  false) \
+  X(fwd2_d128,       128, 4, 2,   true,  false, 8,  false, false, false) \
+  X(fwd2_d32_rot,    32,  4, 3,   false, true,  2,  false, true,  false) \
+  X(fwd2_d64_rot,    64,  4, 3,   false, true,  4,  false, true,  false) \
+  X(fwd2_d32_rel,    32,  4, 2,   true,  false, 2,  true,  false, false) \
+  X(fwd2_d64_rel,    64,  4, 2,   true,  false, 4,  true,  false, false) \
+  X(fwd2_d128_rel,   128, 4, 2,   true,  false, 8,  true,  false, false) \
+  X(fwd2_d32_drop,   32,  4, 3,   false, false, 2,  false, true,  true)  \
+  X(fwd2_d64_k3_drop, 64, 4, 2,   false, false, 3,  false, true,  true)  \
+  X(fwd2_d64_drop,   64,  4, 2,   false, false, 4,  false, true,  true)
+
+// (waves 4-7 staggered, the previous tile's dQ first: DeiT-S 53.6 -> 53.2 us, CaiT-S24
+// 130.7 -> 128.3 us, profiles/r06g_bwd3_stagger_ab.txt; same sums, bit-identical results)
+//  row name         DP  NW KPW ROT    NSU DROP
+#define SAE_BWD3_TABLE(X)                            \
+  X(bwd3_d32,        32, 8, 1,  false, 2,  false)    \
+  X(bwd3_d64_k3,     64, 8, 1,  false, 3,  false)    \
+  X(bwd3_d64,        64, 8, 1,  false, 4,  false)    \
+  X(bwd3_d32_rot,    32, 8, 1,  true,  2,  false)    \
+  X(bwd3_d64_rot,    64, 8, 1,  true,  4,  false)    \
+  X(bwd3_d32_drop,   32, 8, 1,  false, 2,  true)     \
+  X(bwd3_d64_k3_drop, 64, 8, 1, false, 3,  true)     \
+  X(bwd3_d64_drop,   64, 8, 1,  false, 4,  true)
+
+//  row name         BWD    NCH
+#define SAE_CLS_TABLE(X)          \
+  X(cls_fwd_1,       false, 1)    \
+  X(cls_fwd_2,       false, 2)    \
+  X(cls_bwd_1,       true,  1)    \
+  X(cls_bwd_2,       true,  2)
+
+// one launch of a route: a table row, one of bwd_agpr.hip's two functions, or the v1 launcher
+#define SAE_ROW(name, ...) name,
+enum class Inst {
+  SAE_FWD2_TABLE(SAE_ROW) SAE_BWD3_TABLE(SAE_ROW) SAE_BWD2_DQ_TABLE(SAE_ROW) SAE_BWD2_DKDV_TABLE(SAE_ROW)
+  SAE_CLS_TABLE(SAE_ROW)
+  bwd2_d128_agpr,          // bwd2_agpr128: both passes
+  bwd2_dq_d128_rel_agpr,   // bwd2_agpr128_rel_dq
+  v1_fwd,
+  v1_bwd,
+};
+#undef SAE_ROW
+
+const char* inst_name(Inst i) {
+  switch (i) {
+#define SAE_ROW(name, ...) \
+  case Inst::name: return #name;
+    SAE_FWD2_TABLE(SAE_ROW) SAE_BWD3_TABLE(SAE_ROW) SAE_BWD2_DQ_TABLE(SAE_ROW) SAE_BWD2_DKDV_TABLE(SAE_ROW)
+    SAE_CLS_TABLE(SAE_ROW)
+#undef SAE_ROW
+    case Inst::bwd2_d128_agpr: return "bwd2_dq_d128_agpr+bwd2_dkdv_d128_agpr";   // SAE_BWD2_AGPR_TABLE's names
+    case Inst::bwd2_dq_d128_rel_agpr: return "bwd2_dq_d128_rel_agpr";
+    case Inst::v1_fwd: return "v1_fwd";
+    case Inst::v1_bwd: return "v1_bwd";
   }
+  return "?";
 }
 
-// lean bf16 backward (bwd2.h): dQ pass (publishes delta) then dK/dV pass, both at two waves per SIMD
-template <int DP, bool ROT = false> int bwd2_run_default(hipStream_t st, const AttnArgs& a) {
-  return bwd2_run<DP, 4, 2, 4, 2, ROT>(st, a);
+int run_inst(Inst i, const V1& v1, hipStream_t st, const AttnArgs& a) {
+  switch (i) {
+#define SAE_F2(name, ...) \
+  case Inst::name: return fwd2_run<__VA_ARGS__>(st, a);
+#define SAE_B3(name, ...) \
+  case Inst::name: return bwd3_run<__VA_ARGS__>(st, a);
+#define SAE_DQ(name, ...) \
+  case Inst::name: return bwd2_dq_run<__VA_ARGS__>(st, a);
+#define SAE_DKDV(name, ...) \
+  case Inst::name: return bwd2_dkdv_run<__VA_ARGS__>(st, a);
+#define SAE_CLS(name, ...) \
+  case Inst::name: return cls_run<__VA_ARGS__>(st, a);
+    SAE_FWD2_TABLE(SAE_F2) SAE_BWD3_TABLE(SAE_B3) SAE_BWD2_DQ_TABLE(SAE_DQ) SAE_BWD2_DKDV_TABLE(SAE_DKDV)
+    SAE_CLS_TABLE(SAE_CLS)
+#undef SAE_F2
+#undef SAE_B3
+#undef SAE_DQ
+#undef SAE_DKDV
+#undef SAE_CLS
+    case Inst::bwd2_d128_agpr: return bwd2_agpr128(st, a);
+    case Inst::bwd2_dq_d128_rel_agpr: return bwd2_agpr128_rel_dq(st, a);
+    case Inst::v1_fwd: return dispatch<FwdL>(v1, st, a);
+    case Inst::v1_bwd: return dispatch<BwdL>(v1, st, a);
+  }
+  return fail(SAE_EINVAL, "attention: bad instance %d", (int)i);
 }
 
-// single-pass bf16 backward (bwd3.h): one workgroup per (batch, head) holding all Nk <= 256 keys
-// (8 waves x 32 keys, two waves per SIMD); longer key ranges take the two-pass bwd2
-constexpr int kB3Keys = 256;
+// ------------------------------------------------------------------------------- the plan
+// The one routing decision of the attention entry points: sae_attn_route reports it, the entry
+// points launch it.  Pure: no HIP call, no pointer; the caller reads the dev knob.
+struct AttnFacts {
+  int pass, form;   // SAE_PASS_*, SAE_FORM_*
+  int dtype, D, dp, Nq, Nk;
+  bool vec;         // desc_vec: 16-byte aligned strides, head_dim and pointers
+  int rel_cols;     // rel_h + rel_w with SAE_FLAG_RELPOS, else 0
+  int var;          // SAE_FWD_VARIANT / SAE_BWD_VARIANT: 1 forces v1, 2 (backward) skips bwd3
+};
 
-template <int DP, int NW, int KPW, bool ROT = false, int NSU = DP / 16, bool DROP = false>
-int bwd3_run(hipStream_t st, const AttnArgs& a) {
-  using C = B3<DP, NW, KPW>;
-  static_assert(C::BK == kB3Keys, "bwd3 dispatch assumes 256-key blocks");
-  if (a.Nk > C::BK) return fail(SAE_EINVAL, "bwd3: %d keys > %d", a.Nk, C::BK);
-  return launch("attn_bwd3", attn_bwd3_kernel<DP, NW, KPW, ROT, NSU, DROP>, (long long)a.H * a.B, dim3(64 * NW), C::LDS, st,
-                a);
+struct AttnPlan {
+  int n;
+  Inst step[2];
+  V1 v1;   // the v1 steps' instance
+};
+
+int route(AttnPlan* p, Inst s0) {
+  p->n = 1;
+  p->step[0] = s0;
+  return SAE_OK;
+}
+int route(AttnPlan* p, Inst s0, Inst s1) {
+  p->n = 2;
+  p->step[0] = s0;
+  p->step[1] = s1;
+  return SAE_OK;
+}
+
+int attn_plan(const AttnFacts& f, AttnPlan* p) {
+  using I = Inst;
+  const bool bwd = f.pass == SAE_PASS_BWD, bf16 = f.dtype == SAE_DTYPE_BF16, rel = f.rel_cols > 0;
+  const bool d32 = f.dp == 32;
+  const bool k3 = f.dp == 64 && f.D <= 48;    // CaiT head_dim 48 in 64-wide tiles: three k-steps
+  const bool one_pass = f.Nk <= kB3Keys;      // bwd3 holds every key in one workgroup
+  p->v1 = V1{f.dtype, f.dp, f.vec, rel, f.form == SAE_FORM_DROPOUT};
+
+  if (f.form == SAE_FORM_ROTARY) {   // rotary rides on the lean bf16 kernels only
+    if (!bf16 || !f.vec || rel || f.dp > 64)
+      return fail(SAE_EUNSUPPORTED, "rotary: fused only on the bf16 path with head_dim <= 64 (16-byte aligned "
+                  "strides, no flags)");
+    if (!bwd) return route(p, d32 ? I::fwd2_d32_rot : I::fwd2_d64_rot);
+    if (one_pass) return route(p, d32 ? I::bwd3_d32_rot : I::bwd3_d64_rot);
+    return d32 ? route(p, I::bwd2_dq_d32_rot, I::bwd2_dkdv_d32_rot) : route(p, I::bwd2_dq_d64_rot, I::bwd2_dkdv_d64_rot);
+  }
+
+  if (f.form == SAE_FORM_DROPOUT) {
+    // the lean kernels' DROP instances: aligned strides, head_dim <= 64, more than one query row;
+    // the v1 DROP instances cover the rest of the plain envelope
+    if (bf16 && f.vec && f.dp <= 64 && f.Nq > 1) {
+      if (!bwd) return route(p, d32 ? I::fwd2_d32_drop : k3 ? I::fwd2_d64_k3_drop : I::fwd2_d64_drop);
+      if (one_pass) return route(p, d32 ? I::bwd3_d32_drop : k3 ? I::bwd3_d64_k3_drop : I::bwd3_d64_drop);
+      return d32 ? route(p, I::bwd2_dq_d32_drop, I::bwd2_dkdv_d32_drop)
+                 : route(p, I::bwd2_dq_d64_drop, I::bwd2_dkdv_d64_drop);
+    }
+    return route(p, bwd ? I::v1_bwd : I::v1_fwd);
+  }
+
+  const bool lean = f.var != 1 && bf16 && f.vec;
+  if (lean && !rel && f.Nq == 1 && f.Nk <= kClsMaxKeys) {
+    if (bwd) return route(p, f.D > 64 ? I::cls_bwd_2 : I::cls_bwd_1);
+    return route(p, f.D > 64 ? I::cls_fwd_2 : I::cls_fwd_1);
+  }
+  if (lean && !rel) {
+    if (!bwd) return route(p, d32 ? I::fwd2_d32 : k3 ? I::fwd2_d64_k3 : f.dp == 64 ? I::fwd2_d64 : I::fwd2_d128);
+    if (one_pass && f.var != 2 && f.dp <= 64) return route(p, d32 ? I::bwd3_d32 : k3 ? I::bwd3_d64_k3 : I::bwd3_d64);
+    if (d32) return route(p, I::bwd2_dq_d32, I::bwd2_dkdv_d32);
+    if (f.dp == 64) return route(p, I::bwd2_dq_d64, I::bwd2_dkdv_d64);
+    // head_dim 128 (BoTNet): the dK / dV pass at one wave per SIMD (the dK / dV accumulators of 32
+    // keys x 128 columns plus the K / V fragments need more than half the register file), built in
+    // the AGPR translation unit (bwd_agpr.hip: accumulators in AGPRs, no spills; bot14 bwd
+    // 222 -> 216 us, bot7 49 -> 47 us same box, profiles/r03f_bot_agpr_ab.txt)
+    return route(p, I::bwd2_d128_agpr);
+  }
+  // BoTNet relative logits on the lean kernels: the table columns (Hs + Ws) fit the two extra
+  // score k-steps; larger grids (up to 64 x 64) and fp32 take the v1 kernels
+  if (lean && rel && f.rel_cols <= kRelCols) {
+    if (!bwd) return route(p, d32 ? I::fwd2_d32_rel : f.dp == 64 ? I::fwd2_d64_rel : I::fwd2_d128_rel);
+    if (d32) return route(p, I::bwd2_dq_d32_rel, I::bwd2_dkdv_d32_rel);
+    if (f.dp == 64) return route(p, I::bwd2_dq_d64_rel, I::bwd2_dkdv_d64_rel);
+    // head_dim 128 with relative logits: at 14 x 14 the dQ pass at one wave per SIMD in the AGPR
+    // unit (its relative-logit state spills 75 VGPRs at two waves per SIMD): bot14+rel bwd
+    // 315 -> 298 us; the 7 x 7 grid keeps the two-wave dQ pass (59 vs 67 us).  The dK / dV pass
+    // is this unit's instance at either size.
+    return route(p, f.Nk < 128 ? I::bwd2_dq_d128_rel : I::bwd2_dq_d128_rel_agpr, I::bwd2_dkdv_d128_rel);
+  }
+  return route(p, bwd ? I::v1_bwd : I::v1_fwd);
+}
+
+AttnFacts attn_facts(const sae_attn_desc* d, int pass, int form, bool vec) {
+  return AttnFacts{pass, form, d->dtype, d->head_dim, pick_dp(d->head_dim), d->seq_q, d->seq_k, vec,
+                   (d->flags & SAE_FLAG_RELPOS) ? d->rel_h + d->rel_w : 0,
+                   dev_knob(pass == SAE_PASS_BWD ? "SAE_BWD_VARIANT" : "SAE_FWD_VARIANT")};
+}
+
+int run_plan(const AttnPlan& p, hipStream_t st, const AttnArgs& a) {
+  for (int i = 0; i < p.n; ++i)
+    if (int rc = run_inst(p.step[i], p.v1, st, a)) return rc;
+  return SAE_OK;
+}
+
+// the route's name: its launches in order, the v1 steps with their instance
+std::string plan_name(const AttnPlan& p) {
+  std::string s;
+  for (int i = 0; i < p.n; ++i) {
+    s += i ? "+" : "";
+    if (p.step[i] != Inst::v1_fwd && p.step[i] != Inst::v1_bwd) {
+      s += inst_name(p.step[i]);
+      continue;
+    }
+    const std::string inst = std::string(p.v1.dtype == SAE_DTYPE_BF16 ? "_bf16_d" : "_f32_d") + std::to_string(p.v1.dp) +
+                             (p.v1.vec ? "" : "_scalar") + (p.v1.rel ? "_rel" : p.v1.drop ? "_drop" : "");
+    s += p.step[i] == Inst::v1_fwd ? "v1_fwd" + inst : "v1_bwd_dq" + inst + "+v1_bwd_dkdv" + inst;   // BwdL: two passes
+  }
+  return s;
 }
 
 // ------------------------------------------------------------------------------- dropout
-// Attention-probability dropout (dropout.h).  The v1 kernels' DROP instances cover the whole
-// envelope of the plain entry points with flags == 0 (fp32, unaligned strides or head_dim,
-// head_dim > 64, a single query row).
+// Attention-probability dropout (dropout.h) on the envelope of the plain entry points with
+// flags == 0.
 struct DropCall {
   const unsigned long long* rng;
   unsigned stream_id, thr;
@@ -173,65 +376,31 @@ void fill_drop(AttnArgs& a, const DropCall& c) {
   a.drop_inv = 256.f / (float)(256 - (int)c.thr);
 }
 
+int drop_desc_check(const sae_attn_desc* d) {
+  if (!d) return fail(SAE_EINVAL, "desc is NULL");
+  if (d->flags != 0)
+    return fail(SAE_EUNSUPPORTED, "dropout: flags 0x%x are not supported (no relative logits)", d->flags);
+  return SAE_OK;
+}
+
 // T = clamp(lrintf(rate * 256), 0, 255): a rate below 1 / 512 rounds to T = 0, no dropout
 int drop_check(const sae_attn_desc* d, float rate, const uint64_t* rng, unsigned* thr) {
   if (!(rate >= 0.f && rate < 1.f)) return fail(SAE_EINVAL, "dropout rate %g is outside [0, 1)", (double)rate);
   if (!rng) return fail(SAE_EINVAL, "dropout: rng must be non-NULL");
-  if (!d) return fail(SAE_EINVAL, "desc is NULL");
-  if (d->flags != 0)
-    return fail(SAE_EUNSUPPORTED, "dropout: flags 0x%x are not supported (no relative logits)", d->flags);
+  if (int rc = drop_desc_check(d)) return rc;
   *thr = (unsigned)std::min(255L, std::max(0L, lrintf(rate * 256.f)));
   return SAE_OK;
 }
 
-// the lean bf16 kernels' DROP instances: aligned strides, head_dim <= 64, more than one query row
-bool drop_lean(const sae_attn_desc* d, bool vec, int dp) {
-  return d->dtype == SAE_DTYPE_BF16 && vec && dp <= 64 && d->seq_q > 1;
-}
-
-template <typename T, int DP, bool VEC> struct FwdDropL {
-  static int run(hipStream_t st, const AttnArgs& a) {
-    const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
-    const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK);
-    return launch("attn_fwd_drop", attn_fwd_kernel<T, DP, VEC, false, true>, grid, dim3(256), lds, st, a);
-  }
-};
-
-template <typename T, int DP, bool VEC> struct BwdDropL {
-  static int run(hipStream_t st, const AttnArgs& a) {
-    {  // dQ (+ delta) first, as in BwdL
-      const long long grid = (long long)((a.Nq + kBQ - 1) / kBQ) * a.H * a.B;
-      const size_t lds = nbuf<T, DP>() * 2 * Img<T, DP>::bytes(kBK);
-      if (int rc = launch("attn_bwd_dq_drop", attn_bwd_dq_kernel<T, DP, VEC, false, true>, grid, dim3(256), lds, st, a))
-        return rc;
-    }
-    const long long grid = (long long)((a.Nk + kBKV - 1) / kBKV) * a.H * a.B;
-    const size_t lds = nbuf<T, DP>() * (2 * Img<T, DP>::bytes(kBQT) + 2 * kBQT * sizeof(float));
-    return launch("attn_bwd_dkdv_drop", attn_bwd_dkdv_kernel<T, DP, VEC, false, true>, grid, dim3(256), lds, st, a);
-  }
-};
-
-template <template <typename, int, bool> class L, typename... Args>
-int dispatch_drop(int dtype, int dp, bool vec, Args&&... args) {
-#define SAE_CASE(T, DPV) \
-  if (dp == DPV) return vec ? L<T, DPV, true>::run(args...) : L<T, DPV, false>::run(args...);
-  if (dtype == SAE_DTYPE_BF16) {
-    SAE_CASE(__bf16, 32) SAE_CASE(__bf16, 64) SAE_CASE(__bf16, 128)
-  } else {
-    SAE_CASE(float, 32) SAE_CASE(float, 64) SAE_CASE(float, 128)
-  }
-#undef SAE_CASE
-  return fail(SAE_EUNSUPPORTED, "no dropout kernel instance for dtype %d dp %d", dtype, dp);
-}
-
+// ------------------------------------------------------- entry points: validate, fill, plan, launch
 int attn_fwd_impl(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v,
                   const float* bias_h, const float* bias_w, void* o, float* lse, const RopeTab* rope,
                   const DropCall* drop = nullptr) {
   int rc = validate(d, false);
   if (rc) return rc;
   if (!q || !k || !v || !o) return fail(SAE_EINVAL, "q/k/v/o must be non-NULL");
-  const bool rel = d->flags & SAE_FLAG_RELPOS;
-  if (rel && (!bias_h || !bias_w)) return fail(SAE_EINVAL, "SAE_FLAG_RELPOS needs bias_h and bias_w");
+  if ((d->flags & SAE_FLAG_RELPOS) && (!bias_h || !bias_w))
+    return fail(SAE_EINVAL, "SAE_FLAG_RELPOS needs bias_h and bias_w");
   AttnArgs a;
   fill_args(a, d);
   a.q = q;
@@ -241,41 +410,12 @@ int attn_fwd_impl(void* stream, const sae_attn_desc* d, const void* q, const voi
   a.lse = lse;
   a.bias_h = bias_h;
   a.bias_w = bias_w;
-  const bool vec = desc_vec(d, {q, k, v, o}, false);
-  const int var = dev_knob("SAE_FWD_VARIANT");
-  hipStream_t st = (hipStream_t)stream;
-  const int dp = pick_dp(d->head_dim);
-  if (rope) {   // rotary rides on the lean bf16 kernels only, in the envelope of sae_attn_bwd_rotary
-    if (d->dtype != SAE_DTYPE_BF16 || !vec || rel || d->flags || dp > 64)
-      return fail(SAE_EUNSUPPORTED, "rotary: fused only on the bf16 path with head_dim <= 64 (16-byte aligned "
-                  "strides, no flags)");
-    a.rope = *rope;
-    if (dp == 32) return fwd2_dispatch<32, true>(st, a);
-    return fwd2_dispatch<64, true>(st, a);
-  }
-  if (drop) {
-    fill_drop(a, *drop);
-    if (drop_lean(d, vec, dp)) {
-      // the lean forward's D <= 64 variant (VALU row sum, FIX) with the dropped P zeroed; at DP 64
-      // the Philox state does not fit three waves per SIMD (5 / 16 VGPRs spilled): two there
-      if (dp == 32) return fwd2_run<32, 4, 3, false, false, 2, false, true, true>(st, a);
-      if (d->head_dim <= 48) return fwd2_run<64, 4, 2, false, false, 3, false, true, true>(st, a);
-      return fwd2_run<64, 4, 2, false, false, 4, false, true, true>(st, a);
-    }
-    return dispatch_drop<FwdDropL>(d->dtype, dp, vec, st, a);
-  }
-  if (var != 1 && vec && cls_ok(d)) return cls_run<false>(st, a);
-  if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && !rel) {
-    if (dp == 32) return fwd2_dispatch<32>(st, a);
-    if (dp == 64) return fwd2_dispatch<64>(st, a);
-    if (dp == 128) return fwd2_dispatch<128>(st, a);
-  }
-  if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && rel && rel_lean(a)) {   // BoTNet
-    if (dp == 32) return fwd2_run<32, 4, 2, true, false, 2, true>(st, a);
-    if (dp == 64) return fwd2_run<64, 4, 2, true, false, 4, true>(st, a);
-    return fwd2_run<128, 4, 2, true, false, 8, true>(st, a);
-  }
-  return dispatch<FwdL>(d->dtype, dp, vec, rel, st, a);
+  if (rope) a.rope = *rope;
+  if (drop) fill_drop(a, *drop);
+  AttnPlan p;
+  const int form = rope ? SAE_FORM_ROTARY : drop ? SAE_FORM_DROPOUT : SAE_FORM_PLAIN;
+  if ((rc = attn_plan(attn_facts(d, SAE_PASS_FWD, form, desc_vec(d, {q, k, v, o}, false)), &p))) return rc;
+  return run_plan(p, (hipStream_t)stream, a);
 }
 
 int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, const void* k, const void* v,
@@ -286,8 +426,7 @@ int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, const voi
   if (rc) return rc;
   if (!q || !k || !v || !o || !lse || !dout || !dq || !dk || !dv || !workspace)
     return fail(SAE_EINVAL, "q/k/v/o/lse/dout/dq/dk/dv/workspace must be non-NULL");
-  const bool rel = d->flags & SAE_FLAG_RELPOS;
-  if (rel && (!bias_h || !bias_w || !dbias_h || !dbias_w))
+  if ((d->flags & SAE_FLAG_RELPOS) && (!bias_h || !bias_w || !dbias_h || !dbias_w))
     return fail(SAE_EINVAL, "SAE_FLAG_RELPOS needs bias_h, bias_w, dbias_h, dbias_w");
   AttnArgs a;
   fill_args(a, d);
@@ -305,61 +444,13 @@ int attn_bwd_impl(void* stream, const sae_attn_desc* d, const void* q, const voi
   a.bias_w = bias_w;
   a.dbias_h = dbias_h;
   a.dbias_w = dbias_w;
-  const bool vec = desc_vec(d, {q, k, v, o, dout, dq, dk, dv}, true);
-  const int var = dev_knob("SAE_BWD_VARIANT");
-  hipStream_t st = (hipStream_t)stream;
-  const int dp = pick_dp(d->head_dim);
-  if (rope) {   // rotary rides on the lean bf16 kernels only
-    if (d->dtype != SAE_DTYPE_BF16 || !vec || rel || d->flags || dp > 64)
-      return fail(SAE_EUNSUPPORTED, "rotary: fused only on the bf16 path with head_dim <= 64 (16-byte aligned "
-                  "strides, no flags)");
-    a.rope = *rope;
-    if (a.Nk <= kB3Keys)
-      return dp == 32 ? bwd3_run<32, 8, 1, true, 2>(st, a) : bwd3_run<64, 8, 1, true, 4>(st, a);
-    return dp == 32 ? bwd2_run_default<32, true>(st, a) : bwd2_run_default<64, true>(st, a);
-  }
-  if (drop) {
-    fill_drop(a, *drop);
-    if (drop_lean(d, vec, dp)) {
-      if (a.Nk <= kB3Keys) {
-        if (dp == 32) return bwd3_run<32, 8, 1, false, 2, true>(st, a);
-        if (d->head_dim <= 48) return bwd3_run<64, 8, 1, false, 3, true>(st, a);
-        return bwd3_run<64, 8, 1, false, 4, true>(st, a);
-      }
-      if (dp == 32) return bwd2_run<32, 4, 2, 4, 2, false, false, true>(st, a);
-      return bwd2_run<64, 4, 2, 4, 2, false, false, true>(st, a);
-    }
-    return dispatch_drop<BwdDropL>(d->dtype, dp, vec, st, a);
-  }
-  if (var != 1 && vec && cls_ok(d)) return cls_run<true>(st, a);
-  if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && !rel) {
-    if (a.Nk <= kB3Keys && var != 2 && dp <= 64) {
-      // (waves 4-7 staggered, the previous tile's dQ first: DeiT-S 53.6 -> 53.2 us, CaiT-S24
-      // 130.7 -> 128.3 us, profiles/r06g_bwd3_stagger_ab.txt; same sums, bit-identical results)
-      if (dp == 32) return bwd3_run<32, 8, 1, false, 2>(st, a);
-      if (dp == 64 && d->head_dim <= 48) return bwd3_run<64, 8, 1, false, 3>(st, a);   // CaiT head_dim 48
-      if (dp == 64) return bwd3_run<64, 8, 1, false, 4>(st, a);
-    }
-    if (dp == 32) return bwd2_run_default<32>(st, a);
-    if (dp == 64) return bwd2_run_default<64>(st, a);
-    // head_dim 128 (BoTNet): the dK / dV pass at one wave per SIMD (the dK / dV accumulators of 32
-    // keys x 128 columns plus the K / V fragments need more than half the register file), built in
-    // the AGPR translation unit (bwd_agpr.hip: accumulators in AGPRs, no spills; bot14 bwd
-    // 222 -> 216 us, bot7 49 -> 47 us same box, profiles/r03f_bot_agpr_ab.txt)
-    return bwd2_agpr128(st, a);
-  }
-  if (var != 1 && d->dtype == SAE_DTYPE_BF16 && vec && rel && rel_lean(a)) {   // BoTNet relative logits
-    if (dp == 32) return bwd2_run<32, 4, 2, 4, 2, false, true>(st, a);
-    if (dp == 64) return bwd2_run<64, 4, 2, 4, 1, false, true>(st, a);
-    // head_dim 128 with relative logits: at 14 x 14 the dQ pass at one wave per SIMD in the AGPR
-    // unit (its relative-logit state spills 75 VGPRs at two waves per SIMD): bot14+rel bwd
-    // 315 -> 298 us; the 7 x 7 grid keeps the two-wave dQ pass (59 vs 67 us).  The dK / dV pass
-    // is this unit's instance at either size.
-    if (a.Nk < 128) return bwd2_run<128, 4, 2, 4, 1, false, true>(st, a);
-    if (int rc2 = bwd2_agpr128_rel_dq(st, a)) return rc2;
-    return bwd2_dkdv_run<128, 4, 1, false, true>(st, a);
-  }
-  return dispatch<BwdL>(d->dtype, dp, vec, rel, st, a);
+  if (rope) a.rope = *rope;
+  if (drop) fill_drop(a, *drop);
+  AttnPlan p;
+  const int form = rope ? SAE_FORM_ROTARY : drop ? SAE_FORM_DROPOUT : SAE_FORM_PLAIN;
+  if ((rc = attn_plan(attn_facts(d, SAE_PASS_BWD, form, desc_vec(d, {q, k, v, o, dout, dq, dk, dv}, true)), &p)))
+    return rc;
+  return run_plan(p, (hipStream_t)stream, a);
 }
 
 int rel_validate(int B, int H, int Hs, int Ws, int D, int dtype) {
@@ -424,6 +515,24 @@ int sae_attn_bwd_rotary(void* stream, const sae_attn_desc* d, const void* q, con
   const RopeTab t = make_rope(d, sin_tab, cos_tab);
   return attn_bwd_impl(stream, d, q, k, v, o, lse, dout, nullptr, nullptr, dq, dk, dv, nullptr, nullptr, workspace,
                        &t);
+}
+
+// host-only: the plan of the entry point of that pass and form, by name (no HIP call)
+const char* sae_attn_route(const sae_attn_desc* d, int32_t pass, int32_t form, int32_t aligned) {
+  static thread_local std::string name;
+  if (route_args_check(pass, form)) return nullptr;
+  if (form == SAE_FORM_ROTARY) {
+    if (!d) return fail(SAE_EINVAL, "NULL descriptor"), nullptr;
+    if (rope_dim_check(d)) return nullptr;
+  }
+  if (form == SAE_FORM_DROPOUT && drop_desc_check(d)) return nullptr;
+  const bool bwd = pass == SAE_PASS_BWD;
+  if (validate(d, bwd)) return nullptr;
+  AttnPlan p;
+  if (attn_plan(attn_facts(d, pass, form, aligned && desc_strides_vec(d, bwd)), &p)) return nullptr;
+  name = plan_name(p);
+  ok();
+  return name.c_str();
 }
 
 // --------------------------------------------------------------------------------- dropout

@@ -7,12 +7,22 @@
 
 namespace sae {
 
+namespace {
+#define SAE_ROW(name, pass, ...) \
+  int name(hipStream_t st, const AttnArgs& a) { return bwd2_##pass##_run<__VA_ARGS__>(st, a); }
+SAE_BWD2_AGPR_TABLE(SAE_ROW)
+#undef SAE_ROW
+}  // namespace
+
 // head_dim 128 (BoTNet): the dQ pass at two waves per SIMD, the dK / dV pass at one
-int bwd2_agpr128(hipStream_t st, const AttnArgs& a) { return bwd2_run<128, 4, 2, 4, 1>(st, a); }
+int bwd2_agpr128(hipStream_t st, const AttnArgs& a) {
+  if (int rc = bwd2_dq_d128_agpr(st, a)) return rc;
+  return bwd2_dkdv_d128_agpr(st, a);
+}
 
 // with relative logits at >= 128 keys: the dQ pass at one wave per SIMD (its relative-logit state
-// spills at two).  The dK / dV pass that follows is attn.hip's attn_bwd2_dkdv_kernel<128, 4, 1,
-// false, true>, the VGPR-form instance the 7 x 7 grid runs too: one definition, in one unit.
-int bwd2_agpr128_rel_dq(hipStream_t st, const AttnArgs& a) { return bwd2_dq_run<128, 4, 1, false, true>(st, a); }
+// spills at two).  The dK / dV pass that follows is attn.hip's bwd2_dkdv_d128_rel, the VGPR-form
+// instance the 7 x 7 grid runs too: one definition, in one unit.
+int bwd2_agpr128_rel_dq(hipStream_t st, const AttnArgs& a) { return bwd2_dq_d128_rel_agpr(st, a); }
 
 }  // namespace sae

@@ -62,16 +62,28 @@ template <class Args> void fill_desc(Args& a, const sae_attn_desc* d) {
 }
 
 // 16-byte vector loads and stores: head_dim and every stride in use a whole number of 16-byte
-// chunks, every pointer in `ptrs` 16-byte aligned
-inline bool desc_vec(const sae_attn_desc* d, std::initializer_list<const void*> ptrs, bool bwd) {
+// chunks (the descriptor's half, which the route queries share), every pointer in `ptrs` 16-byte
+// aligned
+inline bool desc_strides_vec(const sae_attn_desc* d, bool bwd) {
   const int epc = 16 / elem_size(d->dtype);
   bool v = d->head_dim % epc == 0 && strides_vec(d->q_stride, epc) && strides_vec(d->k_stride, epc) &&
            strides_vec(d->v_stride, epc) && strides_vec(d->o_stride, epc);
   if (bwd)
     v = v && strides_vec(d->do_stride, epc) && strides_vec(d->dq_stride, epc) && strides_vec(d->dk_stride, epc) &&
         strides_vec(d->dv_stride, epc);
+  return v;
+}
+inline bool desc_vec(const sae_attn_desc* d, std::initializer_list<const void*> ptrs, bool bwd) {
+  bool v = desc_strides_vec(d, bwd);
   for (const void* p : ptrs) v = v && aligned16(p);
   return v;
+}
+
+// pass / form of the route queries (sae_attn_route, sae_th_attn_route)
+inline int route_args_check(int pass, int form) {
+  if ((pass != SAE_PASS_FWD && pass != SAE_PASS_BWD) || form < SAE_FORM_PLAIN || form > SAE_FORM_DROPOUT)
+    return fail(SAE_EINVAL, "route: bad pass %d or form %d", pass, form);
+  return SAE_OK;
 }
 
 // delta [B, H, Nq] fp32 at the head of every backward workspace
@@ -80,12 +92,15 @@ inline size_t delta_bytes(const sae_attn_desc* d) {
 }
 
 // rotary tables of the _rotary entry points: fp32 [max(seq_q, seq_k)][head_dim / 2]
-inline int rope_check(const sae_attn_desc* d, const float* sin_tab, const float* cos_tab) {
-  if (!sin_tab || !cos_tab) return fail(SAE_EINVAL, "rotary: sin_tab / cos_tab must be non-NULL");
-  if (!aligned16(sin_tab) || !aligned16(cos_tab)) return fail(SAE_EINVAL, "rotary: tables must be 16-byte aligned");
+inline int rope_dim_check(const sae_attn_desc* d) {
   if (d->head_dim % 8 || d->head_dim > 64)
     return fail(SAE_EUNSUPPORTED, "rotary: fused rotary needs head_dim %% 8 == 0 and <= 64 (got %d)", d->head_dim);
   return SAE_OK;
+}
+inline int rope_check(const sae_attn_desc* d, const float* sin_tab, const float* cos_tab) {
+  if (!sin_tab || !cos_tab) return fail(SAE_EINVAL, "rotary: sin_tab / cos_tab must be non-NULL");
+  if (!aligned16(sin_tab) || !aligned16(cos_tab)) return fail(SAE_EINVAL, "rotary: tables must be 16-byte aligned");
+  return rope_dim_check(d);
 }
 inline RopeTab make_rope(const sae_attn_desc* d, const float* sin_tab, const float* cos_tab) {
   RopeTab t;

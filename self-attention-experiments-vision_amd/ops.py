@@ -175,14 +175,24 @@ def _rope_tabs(q, k, rope):
     return rotary_tables(max(q.shape[1], k.shape[1]), q.shape[-1], q.device, rope)
 
 
+def _rope_route(route: str, ts) -> bool:
+    """Whether the C ABI's own plan (``sae_attn_route`` / ``sae_th_attn_route``, rotary form) takes
+    the [B, N, H, D] tensors ``ts`` = (q[, k[, v]]); a missing k / v has the layout of the last one."""
+    if ts[0].dtype not in (torch.bfloat16, torch.float32) or any(t.dim() != 4 or t.stride(3) != 1 for t in ts):
+        return False   # nothing a descriptor can say
+    q, k, v = (tuple(ts) + (ts[-1],) * 2)[:3]
+    lib = L.load()
+    d = L.SaeAttnDesc()
+    lib.sae_attn_desc_init(ctypes.byref(d), q.shape[0], q.shape[2], q.shape[1], k.shape[1], q.shape[3],
+                           dtype_code(q.dtype), 1.0)
+    d.q_stride, d.k_stride, d.v_stride = L.s3(_bnh(q)), L.s3(_bnh(k)), L.s3(_bnh(v))
+    aligned = all(t.data_ptr() % 16 == 0 for t in ts)
+    return getattr(lib, route)(ctypes.byref(d), L.SAE_PASS_FWD, L.SAE_FORM_ROTARY, int(aligned)) is not None
+
+
 def rope_fused_ok(*ts: torch.Tensor) -> bool:
-    """Whether the fused-rotary kernels take these [B, N, H, D] tensors (sae_attn_*_rotary:
-    bf16, head_dim % 8 == 0 and <= 64, 16-byte aligned token / head strides)."""
-    t0 = ts[0]
-    D = t0.shape[-1]
-    return (t0.dtype == torch.bfloat16 and D % 8 == 0 and D <= 64 and
-            all(t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(2) % 8 == 0
-                and t.data_ptr() % 16 == 0 for t in ts))
+    """Whether the fused-rotary kernels take these [B, N, H, D] tensors (sae_attn_*_rotary)."""
+    return _rope_route("sae_attn_route", ts)
 
 
 # ------------------------------------------------------------------- attention dropout state
@@ -569,7 +579,7 @@ class _TalkingHeadsPacked(torch.autograd.Function):
 
 
 def _th_rope_ok(q, k, v) -> bool:
-    return rope_fused_ok(q, k, v) and q.shape[2] <= L.SAE_TH_MAX_HEADS
+    return _rope_route("sae_th_attn_route", (q, k, v))
 
 
 def talking_heads_attention_packed(qkv, th1, th2, scale: Optional[float] = None, rotary: Optional[float] = None):

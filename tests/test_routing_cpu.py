@@ -1,4 +1,4 @@
-"""Projection routing (CPU: the routing predicates only, no device needed).
+"""Projection and attention routing (CPU: the routing predicates only, no device needed).
 
 Every forward and input-gradient GEMM of every attention encoder width in the reference's model
 registry (models/create_model.py:6-215 -- ViT-B/L, CaiT XXS..M, CeiT, CvT, TNT inner / outer;
@@ -97,3 +97,215 @@ def test_library_switch():
     finally:
         ops.GEMM_LIB = old
     assert ops.use_gemm_nt(768, 2304)
+
+
+# ------------------------------------------------------------------ attention routing
+# ``sae_attn_route`` / ``sae_th_attn_route`` report the plan the entry points launch (attn.hip
+# attn_plan, th.hip th_plan) by name: the rows of the instance tables, in launch order.  Every
+# expectation below is derived from the dispatch cascade those plans replaced, not from their output.
+FWD, BWD = L.SAE_PASS_FWD, L.SAE_PASS_BWD
+PLAIN, ROT, DROP = L.SAE_FORM_PLAIN, L.SAE_FORM_ROTARY, L.SAE_FORM_DROPOUT
+BF16, F32 = L.SAE_DTYPE_BF16, L.SAE_DTYPE_F32
+
+
+def _desc(lib, Nq, Nk, D, H=4, dtype=BF16, grid=None, B=2):
+    import ctypes
+    d = L.SaeAttnDesc()
+    lib.sae_attn_desc_init(ctypes.byref(d), B, H, Nq, Nk, D, dtype, 0.125)
+    if grid is not None:
+        d.flags, d.rel_h, d.rel_w = L.SAE_FLAG_RELPOS, grid[0], grid[1]
+    return d
+
+
+def _route(lib, fn, d, pas, form, aligned=1):
+    import ctypes
+    r = getattr(lib, fn)(ctypes.byref(d), pas, form, aligned)
+    return None if r is None else r.decode()
+
+
+def _pair(sfx):
+    return f"bwd2_dq_{sfx}+bwd2_dkdv_{sfx}"
+
+
+# (route, pass, form, descriptor arguments): one pin per row of the lean tables
+ATTN_ROWS = [
+    # forward: three waves per SIMD at dp <= 64 (NSU 3 at head_dim <= 48), MFMA row sum at dp 128
+    ("fwd2_d32", FWD, PLAIN, dict(Nq=50, Nk=50, D=32)),
+    ("fwd2_d64_k3", FWD, PLAIN, dict(Nq=50, Nk=50, D=48)),
+    ("fwd2_d64", FWD, PLAIN, dict(Nq=50, Nk=50, D=64)),
+    ("fwd2_d128", FWD, PLAIN, dict(Nq=50, Nk=50, D=128)),
+    ("fwd2_d32_rot", FWD, ROT, dict(Nq=50, Nk=50, D=32)),
+    ("fwd2_d64_rot", FWD, ROT, dict(Nq=50, Nk=50, D=64)),
+    ("fwd2_d64_rot", FWD, ROT, dict(Nq=50, Nk=50, D=48)),      # rotary has no NSU 3 instance
+    ("fwd2_d64_rot", FWD, ROT, dict(Nq=1, Nk=50, D=64)),       # and rides the lean kernel at Nq 1
+    ("fwd2_d32_rel", FWD, PLAIN, dict(Nq=49, Nk=49, D=32, grid=(7, 7))),
+    ("fwd2_d64_rel", FWD, PLAIN, dict(Nq=49, Nk=49, D=64, grid=(7, 7))),
+    ("fwd2_d128_rel", FWD, PLAIN, dict(Nq=49, Nk=49, D=128, grid=(7, 7))),
+    ("fwd2_d32_drop", FWD, DROP, dict(Nq=50, Nk=50, D=32)),
+    ("fwd2_d64_k3_drop", FWD, DROP, dict(Nq=50, Nk=50, D=48)),
+    ("fwd2_d64_drop", FWD, DROP, dict(Nq=50, Nk=50, D=64)),
+    # backward, Nk <= 256 and dp <= 64: the single pass
+    ("bwd3_d32", BWD, PLAIN, dict(Nq=50, Nk=256, D=32)),
+    ("bwd3_d64_k3", BWD, PLAIN, dict(Nq=50, Nk=50, D=40)),
+    ("bwd3_d64", BWD, PLAIN, dict(Nq=50, Nk=50, D=64)),
+    ("bwd3_d32_rot", BWD, ROT, dict(Nq=50, Nk=50, D=32)),
+    ("bwd3_d64_rot", BWD, ROT, dict(Nq=50, Nk=50, D=48)),
+    ("bwd3_d32_drop", BWD, DROP, dict(Nq=50, Nk=50, D=32)),
+    ("bwd3_d64_k3_drop", BWD, DROP, dict(Nq=50, Nk=50, D=48)),
+    ("bwd3_d64_drop", BWD, DROP, dict(Nq=50, Nk=50, D=64)),
+    # backward, longer key ranges: the dQ pass, then the dK / dV pass
+    (_pair("d32"), BWD, PLAIN, dict(Nq=50, Nk=257, D=32)),
+    (_pair("d64"), BWD, PLAIN, dict(Nq=50, Nk=300, D=48)),
+    (_pair("d32_rot"), BWD, ROT, dict(Nq=50, Nk=300, D=32)),
+    (_pair("d64_rot"), BWD, ROT, dict(Nq=50, Nk=300, D=64)),
+    (_pair("d32_drop"), BWD, DROP, dict(Nq=50, Nk=300, D=32)),
+    (_pair("d64_drop"), BWD, DROP, dict(Nq=50, Nk=300, D=48)),
+    # relative logits never take bwd3
+    (_pair("d32_rel"), BWD, PLAIN, dict(Nq=49, Nk=49, D=32, grid=(7, 7))),
+    (_pair("d64_rel"), BWD, PLAIN, dict(Nq=49, Nk=49, D=64, grid=(7, 7))),
+    (_pair("d128_rel"), BWD, PLAIN, dict(Nq=49, Nk=49, D=128, grid=(7, 7))),
+    ("bwd2_dq_d128_rel_agpr+bwd2_dkdv_d128_rel", BWD, PLAIN, dict(Nq=128, Nk=128, D=128, grid=(8, 16))),
+    (_pair("d128_agpr"), BWD, PLAIN, dict(Nq=50, Nk=50, D=128)),
+    # a single query row without relative logits, before the lean kernels
+    ("cls_fwd_1", FWD, PLAIN, dict(Nq=1, Nk=50, D=64)),
+    ("cls_fwd_2", FWD, PLAIN, dict(Nq=1, Nk=50, D=72)),
+    ("cls_bwd_1", BWD, PLAIN, dict(Nq=1, Nk=300, D=32)),
+    ("cls_bwd_2", BWD, PLAIN, dict(Nq=1, Nk=50, D=128)),
+]
+
+ATTN_BASELINE = [
+    ("fwd2_d64", FWD, PLAIN, dict(Nq=197, Nk=197, D=64, H=6)),              # DeiT-S
+    ("bwd3_d64", BWD, PLAIN, dict(Nq=197, Nk=197, D=64, H=6)),
+    (_pair("d64"), BWD, PLAIN, dict(Nq=577, Nk=577, D=64, H=12)),           # ViT-B@384
+    ("cls_fwd_1", FWD, PLAIN, dict(Nq=1, Nk=197, D=48, H=8)),               # CaiT class attention
+    ("cls_bwd_1", BWD, PLAIN, dict(Nq=1, Nk=197, D=48, H=8)),
+    ("fwd2_d128", FWD, PLAIN, dict(Nq=196, Nk=196, D=128)),                 # BoTNet 14 x 14
+    (_pair("d128_agpr"), BWD, PLAIN, dict(Nq=196, Nk=196, D=128)),
+    ("fwd2_d128_rel", FWD, PLAIN, dict(Nq=196, Nk=196, D=128, grid=(14, 14))),
+    ("bwd2_dq_d128_rel_agpr+bwd2_dkdv_d128_rel", BWD, PLAIN, dict(Nq=196, Nk=196, D=128, grid=(14, 14))),
+    ("fwd2_d128", FWD, PLAIN, dict(Nq=49, Nk=49, D=128)),                   # BoTNet 7 x 7
+    (_pair("d128_agpr"), BWD, PLAIN, dict(Nq=49, Nk=49, D=128)),
+    ("fwd2_d128_rel", FWD, PLAIN, dict(Nq=49, Nk=49, D=128, grid=(7, 7))),
+    (_pair("d128_rel"), BWD, PLAIN, dict(Nq=49, Nk=49, D=128, grid=(7, 7))),
+    # a 40 x 40 grid: 80 table columns do not fit the lean kernels' 32
+    ("v1_fwd_bf16_d64_rel", FWD, PLAIN, dict(Nq=1600, Nk=1600, D=64, grid=(40, 40))),
+    ("v1_bwd_dq_bf16_d64_rel+v1_bwd_dkdv_bf16_d64_rel", BWD, PLAIN, dict(Nq=1600, Nk=1600, D=64, grid=(40, 40))),
+    # head_dim 10 is no whole number of 16-byte chunks; fp32 always takes v1
+    ("v1_fwd_bf16_d32_scalar", FWD, PLAIN, dict(Nq=50, Nk=50, D=10)),
+    ("v1_bwd_dq_bf16_d32_scalar+v1_bwd_dkdv_bf16_d32_scalar", BWD, PLAIN, dict(Nq=50, Nk=50, D=10)),
+    ("v1_fwd_f32_d64", FWD, PLAIN, dict(Nq=197, Nk=197, D=64, dtype=F32)),
+    ("v1_bwd_dq_f32_d64+v1_bwd_dkdv_f32_d64", BWD, PLAIN, dict(Nq=1, Nk=197, D=64, dtype=F32)),
+    # dropout: lean at dp <= 64 and Nq > 1 (pinned per row above at 32 / 48 / 64), else v1 DROP
+    ("v1_fwd_bf16_d128_drop", FWD, DROP, dict(Nq=50, Nk=50, D=128)),
+    ("v1_bwd_dq_bf16_d128_drop+v1_bwd_dkdv_bf16_d128_drop", BWD, DROP, dict(Nq=50, Nk=50, D=128)),
+    ("v1_fwd_bf16_d64_drop", FWD, DROP, dict(Nq=1, Nk=197, D=48)),
+    ("v1_bwd_dq_bf16_d32_drop+v1_bwd_dkdv_bf16_d32_drop", BWD, DROP, dict(Nq=1, Nk=197, D=32)),
+    ("v1_fwd_f32_d32_drop", FWD, DROP, dict(Nq=50, Nk=50, D=32, dtype=F32)),
+    ("v1_bwd_dq_bf16_d64_scalar_drop+v1_bwd_dkdv_bf16_d64_scalar_drop", BWD, DROP, dict(Nq=50, Nk=50, D=36)),
+]
+
+
+def _th_bwd(q, kv):
+    return f"th2_bwd_q_{q}+th2_bwd_kv_{kv}+th_reduce"
+
+
+TH_ROWS = [
+    # forward: <= 8 heads LEAN (NSU 3 at 32 < head_dim <= 48), 9..16 heads two per wave
+    ("th2_fwd_d32", FWD, PLAIN, dict(D=32, H=8)),
+    ("th2_fwd_d32_h16", FWD, PLAIN, dict(D=24, H=9)),
+    ("th2_fwd_d32_rot", FWD, ROT, dict(D=32, H=4)),
+    ("th2_fwd_d32_rot_h16", FWD, ROT, dict(D=32, H=16)),
+    ("th2_fwd_d64_k3", FWD, PLAIN, dict(D=48, H=8)),
+    ("th2_fwd_d64", FWD, PLAIN, dict(D=64, H=8)),
+    ("th2_fwd_d64_h16", FWD, PLAIN, dict(D=48, H=16)),
+    ("th2_fwd_d64_rot_k3", FWD, ROT, dict(D=40, H=8)),
+    ("th2_fwd_d64_rot", FWD, ROT, dict(D=56, H=8)),
+    ("th2_fwd_d64_rot_h16", FWD, ROT, dict(D=48, H=12)),
+    # backward: the query pass LEAN at dp 64 and <= 8 heads (with rotary at head_dim <= 48 only)
+    (_th_bwd("d32", "d32"), BWD, PLAIN, dict(D=32, H=8)),
+    (_th_bwd("d32_h16", "d32_h16"), BWD, PLAIN, dict(D=32, H=16)),
+    (_th_bwd("d32_rot", "d32_rot"), BWD, ROT, dict(D=32, H=8)),
+    (_th_bwd("d32_rot_h16", "d32_rot_h16"), BWD, ROT, dict(D=16, H=9)),
+    (_th_bwd("d64_lean_k3", "d64"), BWD, PLAIN, dict(D=48, H=8)),
+    (_th_bwd("d64_lean", "d64"), BWD, PLAIN, dict(D=64, H=4)),
+    (_th_bwd("d64_rot_lean_k3", "d64_rot"), BWD, ROT, dict(D=48, H=8)),
+    (_th_bwd("d64_h16", "d64_h16"), BWD, PLAIN, dict(D=48, H=16)),
+    (_th_bwd("d64_rot", "d64_rot"), BWD, ROT, dict(D=64, H=8)),
+    (_th_bwd("d64_rot_h16", "d64_rot_h16"), BWD, ROT, dict(D=48, H=16)),
+]
+# the one row no release call reaches: the query pass at one workgroup per CU without rotary is what
+# SAE_TH_BWDQ_WIDE selects in the development library
+TH_KNOB_ROWS = {"th2_bwd_q_d64"}
+
+TH_BASELINE = [
+    ("th2_fwd_d64_k3", FWD, PLAIN, dict(Nq=196, Nk=196, D=48, H=8)),        # CaiT-S24 trunk
+    (_th_bwd("d64_lean_k3", "d64"), BWD, PLAIN, dict(Nq=196, Nk=196, D=48, H=8)),
+    ("th_fwd_f32_d64", FWD, PLAIN, dict(D=48, H=8, dtype=F32)),             # fp32 / unaligned: v1
+    ("th_bwd_q_bf16_d32_scalar+th_bwd_kv_bf16_d32_scalar+th_reduce", BWD, PLAIN, dict(D=12, H=4)),
+]
+
+
+def _args(kw):
+    kw = dict(kw)
+    kw.setdefault("Nq", 50)
+    kw.setdefault("Nk", kw["Nq"])
+    return kw
+
+
+@pytest.mark.parametrize("want,pas,form,kw", ATTN_ROWS + ATTN_BASELINE)
+def test_attention_route(lib, want, pas, form, kw):
+    assert _route(lib, "sae_attn_route", _desc(lib, **kw), pas, form) == want
+
+
+@pytest.mark.parametrize("want,pas,form,kw", TH_ROWS + TH_BASELINE)
+def test_talking_heads_route(lib, want, pas, form, kw):
+    assert _route(lib, "sae_th_attn_route", _desc(lib, **_args(kw)), pas, form) == want
+
+
+def test_every_table_row_is_pinned():
+    """A row added to an instance table needs its pin above (the tables are the X-macro lists)."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(L.__file__), "csrc")
+    rows = set()
+    for f in ("attn.hip", "bwd2_run.h", "th.hip"):
+        rows |= set(re.findall(r"^  X\((\w+),", open(os.path.join(csrc, f)).read(), re.M))
+    assert len(rows) >= 12 + 8 + 9 + 9 + 3 + 4 + 10 + 11 + 8, sorted(rows)   # the regex still finds the tables
+    pinned = {step for want, *_ in ATTN_ROWS + TH_ROWS for step in want.split("+")}
+    assert rows - pinned == TH_KNOB_ROWS, sorted(rows - pinned)
+
+
+def test_unaligned_pointers_take_the_scalar_kernels(lib):
+    d = _desc(lib, 50, 50, 64)
+    assert _route(lib, "sae_attn_route", d, FWD, PLAIN, 0) == "v1_fwd_bf16_d64_scalar"
+    assert _route(lib, "sae_attn_route", d, BWD, DROP, 0) == "v1_bwd_dq_bf16_d64_scalar_drop+v1_bwd_dkdv_bf16_d64_scalar_drop"
+    d.k_stride[1] += 4   # a token stride that is no whole number of 16-byte chunks
+    assert _route(lib, "sae_attn_route", d, FWD, PLAIN, 1) == "v1_fwd_bf16_d64_scalar"
+    assert _route(lib, "sae_th_attn_route", d, FWD, PLAIN, 1) == "th_fwd_bf16_d64_scalar"
+
+
+REFUSALS = [
+    ("sae_attn_route", FWD, ROT, 1, dict(Nq=50, Nk=50, D=64, dtype=F32), "rotary: fused only on the bf16 path"),
+    ("sae_attn_route", BWD, ROT, 1, dict(Nq=50, Nk=50, D=128),
+     "rotary: fused rotary needs head_dim % 8 == 0 and <= 64 (got 128)"),
+    ("sae_attn_route", FWD, ROT, 0, dict(Nq=50, Nk=50, D=64), "rotary: fused only on the bf16 path"),
+    ("sae_attn_route", BWD, ROT, 1, dict(Nq=49, Nk=49, D=64, grid=(7, 7)), "rotary: fused only on the bf16 path"),
+    ("sae_attn_route", FWD, DROP, 1, dict(Nq=49, Nk=49, D=64, grid=(7, 7)),
+     "dropout: flags 0x1 are not supported (no relative logits)"),
+    ("sae_attn_route", FWD, PLAIN, 1, dict(Nq=50, Nk=50, D=129), "head_dim 129 > 128 is not supported"),
+    ("sae_th_attn_route", FWD, PLAIN, 1, dict(Nq=50, Nk=50, D=48, H=17),
+     "talking heads needs heads <= 16 and head_dim <= 64"),
+    ("sae_th_attn_route", BWD, PLAIN, 1, dict(Nq=50, Nk=50, D=48, H=9, dtype=F32),
+     "talking heads: 9 heads > 8 on the fp32 / unaligned path"),
+    ("sae_th_attn_route", FWD, ROT, 1, dict(Nq=50, Nk=50, D=48, H=8, dtype=F32),
+     "rotary: fused only on the bf16 talking-heads path (aligned strides)"),
+    ("sae_th_attn_route", BWD, ROT, 0, dict(Nq=50, Nk=50, D=48, H=8),
+     "rotary: fused only on the bf16 talking-heads path (aligned strides)"),
+    ("sae_th_attn_route", FWD, PLAIN, 1, dict(Nq=49, Nk=49, D=48, grid=(7, 7)), "talking heads takes no flags"),
+]
+
+
+@pytest.mark.parametrize("fn,pas,form,aligned,kw,text", REFUSALS)
+def test_route_refusals(lib, fn, pas, form, aligned, kw, text):
+    assert _route(lib, fn, _desc(lib, **kw), pas, form, aligned) is None
+    assert lib.sae_last_error().decode().startswith(text)

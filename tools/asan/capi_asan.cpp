@@ -7,7 +7,8 @@
 //     random item lists, at exact capacity and one short (must refuse, not overrun);
 //   * every workspace-size function over a sweep of shapes (no overflow, no negative sizes);
 //   * the validation of every launcher (bad shapes, strides, alignment, NULLs): the error code and
-//     sae_last_error() text, read back each time.
+//     sae_last_error() text, read back each time;
+//   * the attention route queries against their entry points, over a sweep of descriptors.
 // Launchers whose arguments pass validation would launch: with no GPU the HIP launch fails and
 // the ABI reports SAE_EHIP, which is the expected outcome here (no device memory is touched).
 #include <cstdint>
@@ -212,11 +213,66 @@ static void validation() {
   expect(std::strlen(sae_build_info()) > 0, "build info");
 }
 
+// sae_attn_route / sae_th_attn_route name a route exactly when the matching entry point gets as far
+// as the launch (SAE_EHIP without a GPU) and return NULL exactly when it refuses on the host.
+static void routes_agree() {
+  char* base = static_cast<char*>(fake(1 << 16));
+  float *lse = static_cast<float*>(fake()), *sn = static_cast<float*>(fake()), *cs = static_cast<float*>(fake());
+  float *th1 = static_cast<float*>(fake()), *th2 = static_cast<float*>(fake()), *dth1 = static_cast<float*>(fake()),
+        *dth2 = static_cast<float*>(fake());
+  void* ws = fake();
+  const uint64_t* rng = static_cast<const uint64_t*>(fake());
+  auto launched = [](int rc) { return rc == SAE_EHIP || rc == SAE_OK; };
+  auto refused = [](int rc) { return rc == SAE_EINVAL || rc == SAE_EUNSUPPORTED; };
+  for (int dtype : {SAE_DTYPE_F32, SAE_DTYPE_BF16})
+    for (int D : {8, 10, 32, 40, 48, 64, 128})
+      for (int Nq : {1, 50})
+        for (int Nk : {50, 300})
+          for (int H : {4, 12})
+            for (int aligned : {0, 1})
+              for (int form : {SAE_FORM_PLAIN, SAE_FORM_ROTARY, SAE_FORM_DROPOUT})
+                for (int pass : {SAE_PASS_FWD, SAE_PASS_BWD}) {
+                  sae_attn_desc d;
+                  sae_attn_desc_init(&d, 2, H, Nq, Nk, D, dtype, 0.125f);
+                  // one tensor off the 16-byte grid makes the call unaligned
+                  void *q = base + (aligned ? 0 : 4), *k = base + 4096, *v = base + 8192, *o = base + 12288,
+                       *dout = base + 16384, *dq = base + 20480, *dk = base + 24576, *dv = base + 28672;
+                  int rc, rt = SAE_EUNSUPPORTED;   // talking heads has no dropout entry point
+                  if (form == SAE_FORM_PLAIN) {
+                    rc = pass ? sae_attn_bwd(nullptr, &d, q, k, v, o, lse, dout, nullptr, nullptr, dq, dk, dv, nullptr,
+                                             nullptr, ws)
+                              : sae_attn_fwd(nullptr, &d, q, k, v, nullptr, nullptr, o, lse);
+                    rt = pass ? sae_th_attn_bwd(nullptr, &d, q, k, v, th1, th2, lse, dout, dq, dk, dv, dth1, dth2, ws)
+                              : sae_th_attn_fwd(nullptr, &d, q, k, v, th1, th2, o, lse);
+                  } else if (form == SAE_FORM_ROTARY) {
+                    rc = pass ? sae_attn_bwd_rotary(nullptr, &d, q, k, v, o, lse, dout, sn, cs, dq, dk, dv, ws)
+                              : sae_attn_fwd_rotary(nullptr, &d, q, k, v, sn, cs, o, lse);
+                    rt = pass ? sae_th_attn_bwd_rotary(nullptr, &d, q, k, v, th1, th2, lse, dout, sn, cs, dq, dk, dv,
+                                                       dth1, dth2, ws)
+                              : sae_th_attn_fwd_rotary(nullptr, &d, q, k, v, th1, th2, sn, cs, o, lse);
+                  } else {
+                    rc = pass ? sae_attn_bwd_dropout(nullptr, &d, q, k, v, o, lse, dout, dq, dk, dv, ws, 0.5f, rng, 3)
+                              : sae_attn_fwd_dropout(nullptr, &d, q, k, v, o, lse, 0.5f, rng, 3);
+                  }
+                  const bool ra = sae_attn_route(&d, pass, form, aligned) != nullptr;
+                  expect(ra ? launched(rc) : refused(rc), "sae_attn_route agrees with the entry point");
+                  const bool rh = sae_th_attn_route(&d, pass, form, aligned) != nullptr;
+                  expect(rh ? launched(rt) : refused(rt), "sae_th_attn_route agrees with the entry point");
+                }
+  expect(sae_attn_route(nullptr, SAE_PASS_FWD, SAE_FORM_PLAIN, 1) == nullptr, "route: null desc");
+  expect(sae_th_attn_route(nullptr, SAE_PASS_FWD, SAE_FORM_ROTARY, 1) == nullptr, "th route: null desc");
+  sae_attn_desc d;
+  sae_attn_desc_init(&d, 1, 1, 16, 16, 64, SAE_DTYPE_BF16, 0.125f);
+  expect(sae_attn_route(&d, 2, SAE_FORM_PLAIN, 1) == nullptr && sae_attn_route(&d, SAE_PASS_FWD, 3, 1) == nullptr,
+         "route: bad pass / form");
+}
+
 int main() {
   std::mt19937 rng(1234);
   adamw_plans(rng);
   workspace_sizes();
   validation();
+  routes_agree();
   std::printf("capi_asan: %d checks, %d failed\n", g_checks, g_fail);
   return g_fail ? 1 : 0;
 }
