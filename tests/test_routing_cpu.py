@@ -9,6 +9,7 @@ The rocprofv3 step profiles confirm on the GPU that no library GEMM runs (profil
 import pytest
 
 import sae_vision_amd.ops as ops
+from _layouts import desc as _desc, route as _route   # one way to build a descriptor, shared with the layout matrix
 from sae_vision_amd import _lib as L
 
 NONE, TILE128, KTAIL, GEMM8, GEMM8X = 0, 1, 2, 3, 4
@@ -106,21 +107,6 @@ def test_library_switch():
 FWD, BWD = L.SAE_PASS_FWD, L.SAE_PASS_BWD
 PLAIN, ROT, DROP = L.SAE_FORM_PLAIN, L.SAE_FORM_ROTARY, L.SAE_FORM_DROPOUT
 BF16, F32 = L.SAE_DTYPE_BF16, L.SAE_DTYPE_F32
-
-
-def _desc(lib, Nq, Nk, D, H=4, dtype=BF16, grid=None, B=2):
-    import ctypes
-    d = L.SaeAttnDesc()
-    lib.sae_attn_desc_init(ctypes.byref(d), B, H, Nq, Nk, D, dtype, 0.125)
-    if grid is not None:
-        d.flags, d.rel_h, d.rel_w = L.SAE_FLAG_RELPOS, grid[0], grid[1]
-    return d
-
-
-def _route(lib, fn, d, pas, form, aligned=1):
-    import ctypes
-    r = getattr(lib, fn)(ctypes.byref(d), pas, form, aligned)
-    return None if r is None else r.decode()
 
 
 def _pair(sfx):
