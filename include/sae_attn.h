@@ -294,6 +294,14 @@ int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, in
 #define SAE_NT_ROUTE_GEMM8 3          /* persistent 224/256 x 192 tiles (GELU forward at K < 768: 256 x 128 where that loads the CUs more evenly), LDS-DMA (gemm8_nt_kernel) */
 #define SAE_NT_ROUTE_GEMM8X 4         /* ping-pong 256 x 256 tiles, LDS-DMA (gemm8x_nt_kernel) */
 int sae_gemm_nt_route(int32_t M, int32_t N, int32_t K, int32_t epilogue);
+/* The same plan by name (host-only, no device needed; without one it plans for 256 compute units):
+   the row of gemm.hip's instance tables that sae_gemm_nt -- dropout != 0: sae_gemm_nt_gelu_dropout,
+   epilogue SAE_EPI_GELU_GRAD -- launches for the shape, e.g. "g8_192_bm224_plain"; a static string,
+   or NULL with sae_last_error set.  sae_gemm_nt_instance_name(i) is row i of those tables (the image
+   loaders of sae_patch_embed_fwd, "patch_*", included), NULL past the last. */
+const char* sae_gemm_nt_instance(int32_t M, int32_t N, int32_t K, int32_t epilogue,
+                                 int32_t dropout);
+const char* sae_gemm_nt_instance_name(int32_t index);
 /* The SAE_EPI_GELU_GRAD forward with the hidden dropout of ff.py:30 (the mask above over [M][N],
    row = m, col = n, row0 = 0, row_step = 1), h = bf16(acc + bias):
      c = bf16(gelu(h) * keep / pk),  c2 = bf16(gelu'(h) * keep / pk)

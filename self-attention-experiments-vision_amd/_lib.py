@@ -22,6 +22,7 @@ SAE_DTYPE_F32, SAE_DTYPE_BF16 = 0, 1
 SAE_FLAG_RELPOS = 1
 SAE_PASS_FWD, SAE_PASS_BWD = 0, 1
 SAE_FORM_PLAIN, SAE_FORM_ROTARY, SAE_FORM_DROPOUT = 0, 1, 2
+SAE_NT_ROUTE_NONE, SAE_NT_ROUTE_TILE128, SAE_NT_ROUTE_TILE128_KTAIL, SAE_NT_ROUTE_GEMM8, SAE_NT_ROUTE_GEMM8X = range(5)
 SAE_TH_MAX_HEADS = 16
 SAE_TH_MAX_HEAD_DIM = 64
 ABI_VERSION = 1
@@ -90,6 +91,8 @@ _PROTOS = [
     ("sae_gemm_f32", _i32, [_vp, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
     ("sae_gemm_nt", _i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
     ("sae_gemm_nt_route", _i32, [_i32, _i32, _i32, _i32]),
+    ("sae_gemm_nt_instance", ctypes.c_char_p, [_i32, _i32, _i32, _i32, _i32]),
+    ("sae_gemm_nt_instance_name", ctypes.c_char_p, [_i32]),
     ("sae_patch_embed_fwd", _i32, [_vp, ctypes.POINTER(SaePatchDesc), _vp, _vp, _vp, _vp]),
     ("sae_patch_embed_bwd_workspace_bytes", _sz, [ctypes.POINTER(SaePatchDesc)]),
     ("sae_patch_embed_bwd", _i32, [_vp, ctypes.POINTER(SaePatchDesc), _vp, _vp, _vp, _vp, _i32, _vp]),

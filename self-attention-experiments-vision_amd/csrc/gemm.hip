@@ -106,49 +106,183 @@ void f32_plan(int M, int N, int K, int* S, int* kchunk) {
 }
 
 // ------------------------------------------------------------ forward / input-gradient GEMMs
-// one sae_gemm_nt launch: TM x 128 tiles, two LDS stage buffers of BK-deep A and B images
-template <int EPI, class AL> int nt_launch(const NtArgs& g, long long grid, hipStream_t st) {
+// one launch of the 128-row kernel: TM x 128 tiles, two LDS stage buffers of BK-deep A and B
+// images; TM and BK are the operand loader's
+template <int EPI, class AL> int nt_run(const char* name, hipStream_t st, const NtArgs& g) {
   const size_t lds = 2 * (NtRows<AL>::value + kNtT) * NtDepth<AL>::value * 2;
-  return launch("gemm_nt", gemm_nt_kernel<EPI, AL>, grid, dim3(256), lds, st, g);
+  const long long grid = (long long)((g.M + NtRows<AL>::value - 1) / NtRows<AL>::value) * ((g.N + kNtT - 1) / kNtT);
+  return launch(name, gemm_nt_kernel<EPI, AL>, grid, dim3(256), lds, st, g);
 }
-// the same tile shape for each epilogue of the 128-row kernel
-template <class AL> int nt_launch_epi(int epilogue, const NtArgs& g, long long grid, hipStream_t st) {
-  if (epilogue == kEpiGeluDrop) return nt_launch<kEpiGeluDrop, AL>(g, grid, st);
-  return epilogue == SAE_EPI_NONE   ? nt_launch<kEpiNone, AL>(g, grid, st)
-         : epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, AL>(g, grid, st)
-                                    : nt_launch<kEpiDGelu, AL>(g, grid, st);
+
+// one persistent gemm8 launch (BM x BN tiles, one 8-wave workgroup per CU)
+template <int EPI, int BN, int BK, int NS, int BM, int WGM, bool XW>
+int g8_run(const char* name, hipStream_t st, const NtArgs& g, int cus) {
+  const long long tiles = (long long)((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+  return launch(name, gemm8_nt_kernel<EPI, BN, BK, NS, BM, WGM, XW>, std::min<long long>(tiles, cus), dim3(512),
+                g8_lds_bytes<BN, BK, NS, WGM>(), st, g);
+}
+
+// one gemm8x launch (BM x BN tiles, ping-pong wave groups, one tile per workgroup)
+template <int EPI, int BN, int BM> int g8x_run(const char* name, hipStream_t st, const NtArgs& g) {
+  const long long tiles = (long long)((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+  return launch(name, gemm8x_nt_kernel<EPI, BN, true, BM>, tiles, dim3(512), g8x_lds_bytes<BN, BM>(), st, g);
+}
+
+// ------------------------------------------------------------------------ instance tables
+// Every instance of gemm8_nt_kernel, gemm8x_nt_kernel and gemm_nt_kernel is ONE row: the template
+// parameters written once, under their names; the plan and the patch embedding name a row, never
+// a tuple.  Epilogue suffixes: _plain (kEpiNone), _gelu (SAE_EPI_GELU and _GELU_GRAD), _dgelu
+// (SAE_EPI_DGELU and _MUL_AUX), _gelu_drop (sae_gemm_nt_gelu_dropout).
+//
+// gemm8: 224 / 256 x 192 tiles on 2 x 4 waves, and 256 x 128 tiles on 4 x 2 waves (nt_plan).
+// XW, plain 192-wide tiles: whole-row epilogue stores through the shared row image: QKV forward
+// 32.9 -> 31.4 us, DeiT-S step -0.13 % (profiles/r06xw_g8_xw_ab.txt)
+//  row name                 EPI           BN   BK  NS BM   WGM XW
+#define SAE_G8_TABLE(X)                                                \
+  X(g8_192_bm224_plain,      kEpiNone,     192, 64, 2, 224, 2,  true)  \
+  X(g8_192_bm256_plain,      kEpiNone,     192, 64, 2, 256, 2,  true)  \
+  X(g8_192_bm224_gelu,       kEpiGelu,     192, 64, 2, 224, 2,  false) \
+  X(g8_192_bm256_gelu,       kEpiGelu,     192, 64, 2, 256, 2,  false) \
+  X(g8_192_bm224_dgelu,      kEpiDGelu,    192, 64, 2, 224, 2,  false) \
+  X(g8_192_bm256_dgelu,      kEpiDGelu,    192, 64, 2, 256, 2,  false) \
+  X(g8_192_bm224_gelu_drop,  kEpiGeluDrop, 192, 64, 2, 224, 2,  false) \
+  X(g8_192_bm256_gelu_drop,  kEpiGeluDrop, 192, 64, 2, 256, 2,  false) \
+  X(g8_128_wgm4_gelu,        kEpiGelu,     128, 64, 2, 256, 4,  false) \
+  X(g8_128_wgm4_dgelu,       kEpiDGelu,    128, 64, 2, 256, 4,  false) \
+  X(g8_128_wgm4_gelu_drop,   kEpiGeluDrop, 128, 64, 2, 256, 4,  false)
+
+// gemm8x: 224 / 256 x 256 tiles; no GELU' epilogue (g8x_route)
+//  row name                 EPI           BN   BM
+#define SAE_G8X_TABLE(X)                             \
+  X(g8x_bm224_plain,         kEpiNone,     256, 224) \
+  X(g8x_bm256_plain,         kEpiNone,     256, 256) \
+  X(g8x_bm224_gelu,          kEpiGelu,     256, 224) \
+  X(g8x_bm256_gelu,          kEpiGelu,     256, 256) \
+  X(g8x_bm224_gelu_drop,     kEpiGeluDrop, 256, 224) \
+  X(g8x_bm256_gelu_drop,     kEpiGeluDrop, 256, 256)
+
+// The 128-row kernel by operand loader AL = NtRowAT<stage depth, tile rows, K tail>: _k64 the
+// 64-deep stages, _k32 the shallow ones, _tall the 256-token tile (both for the GELU-family
+// epilogues only, nt_plan), _ktail K % 64 != 0; and the four image loaders of sae_patch_embed_fwd
+// (patch.h: NtPatchA<HWCN, F32>), chosen by layout and dtype.
+//  row name                 EPI           AL
+#define SAE_NT128_TABLE(X)                                        \
+  X(nt128_k64_plain,         kEpiNone,     NtRowAT<64>)           \
+  X(nt128_k64_gelu,          kEpiGelu,     NtRowAT<64>)           \
+  X(nt128_k64_dgelu,         kEpiDGelu,    NtRowAT<64>)           \
+  X(nt128_k64_gelu_drop,     kEpiGeluDrop, NtRowAT<64>)           \
+  X(nt128_k32_gelu,          kEpiGelu,     NtRowAT<32>)           \
+  X(nt128_k32_dgelu,         kEpiDGelu,    NtRowAT<32>)           \
+  X(nt128_k32_gelu_drop,     kEpiGeluDrop, NtRowAT<32>)           \
+  X(nt128_tall_gelu,         kEpiGelu,     NtRowAT<32, 256>)      \
+  X(nt128_tall_dgelu,        kEpiDGelu,    NtRowAT<32, 256>)      \
+  X(nt128_tall_gelu_drop,    kEpiGeluDrop, NtRowAT<32, 256>)      \
+  X(nt128_ktail_plain,       kEpiNone,     NtRowAT<64, 128, true>) \
+  X(nt128_ktail_gelu,        kEpiGelu,     NtRowAT<64, 128, true>) \
+  X(nt128_ktail_dgelu,       kEpiDGelu,    NtRowAT<64, 128, true>) \
+  X(nt128_ktail_gelu_drop,   kEpiGeluDrop, NtRowAT<64, 128, true>) \
+  X(patch_nhwc_bf16,         kEpiNone,     NtPatchA<false, false>) \
+  X(patch_nhwc_f32,          kEpiNone,     NtPatchA<false, true>)  \
+  X(patch_hwcn_bf16,         kEpiNone,     NtPatchA<true, false>)  \
+  X(patch_hwcn_f32,          kEpiNone,     NtPatchA<true, true>)
+
+#define SAE_ROW(name, ...) name,
+enum class Inst { SAE_G8_TABLE(SAE_ROW) SAE_G8X_TABLE(SAE_ROW) SAE_NT128_TABLE(SAE_ROW) count };
+#undef SAE_ROW
+
+const char* inst_name(Inst i) {
+  switch (i) {
+#define SAE_ROW(name, ...) \
+  case Inst::name: return #name;
+    SAE_G8_TABLE(SAE_ROW) SAE_G8X_TABLE(SAE_ROW) SAE_NT128_TABLE(SAE_ROW)
+#undef SAE_ROW
+    case Inst::count: break;
+  }
+  return nullptr;
+}
+
+// the launch of a row; `cus` bounds the persistent gemm8 grid (the other kernels: one tile per workgroup)
+int run_inst(Inst i, hipStream_t st, const NtArgs& g, int cus = 0) {
+  switch (i) {
+#define SAE_G8(name, ...) \
+  case Inst::name: return g8_run<__VA_ARGS__>(#name, st, g, cus);
+#define SAE_G8X(name, ...) \
+  case Inst::name: return g8x_run<__VA_ARGS__>(#name, st, g);
+#define SAE_NT(name, ...) \
+  case Inst::name: return nt_run<__VA_ARGS__>(#name, st, g);
+    SAE_G8_TABLE(SAE_G8) SAE_G8X_TABLE(SAE_G8X) SAE_NT128_TABLE(SAE_NT)
+#undef SAE_G8
+#undef SAE_G8X
+#undef SAE_NT
+    case Inst::count: break;
+  }
+  return fail(SAE_EINVAL, "gemm_nt: bad instance %d", (int)i);
+}
+
+// SAE_NT_ROUTE_* of a row: its table, and for the 128-row kernel whether the loader takes a K tail
+int inst_route(Inst i) {
+  switch (i) {
+#define SAE_G8(name, ...) \
+  case Inst::name: return SAE_NT_ROUTE_GEMM8;
+#define SAE_G8X(name, ...) \
+  case Inst::name: return SAE_NT_ROUTE_GEMM8X;
+#define SAE_NT(name, EPI, ...) \
+  case Inst::name: return NtKT<__VA_ARGS__>::value ? SAE_NT_ROUTE_TILE128_KTAIL : SAE_NT_ROUTE_TILE128;
+    SAE_G8_TABLE(SAE_G8) SAE_G8X_TABLE(SAE_G8X) SAE_NT128_TABLE(SAE_NT)
+#undef SAE_G8
+#undef SAE_G8X
+#undef SAE_NT
+    case Inst::count: break;
+  }
+  return SAE_NT_ROUTE_NONE;
+}
+
+// NtArgs.nts of a gemm8 row (0 for the other kernels, which do not read it):
+// epilogue stores non-temporal except for the gelu' multiply on 2 x 4 waves (whose 96-byte row segments then
+// left L2 unmerged: 77 -> 102 MB written); DeiT-S step 8.02 -> 7.96 ms with every epilogue
+// non-temporal, the plain / GELU launches faster and the multiply slower (profiles/r06z_g8_nts_ab.txt).
+// The multiply's aux (gelu'(h)) tile loaded non-temporal: level in isolation, DeiT-S step
+// 8.01 -> 7.85 ms (profiles/r06z4_g8_aux_nt_ab.txt)
+int g8_nts(Inst i) {
+  switch (i) {
+#define SAE_G8(name, EPI, BN, BK, NS, BM, WGM, XW)                                        \
+  case Inst::name:                                                                        \
+    return ((EPI != kEpiDGelu || WGM == 4) && !dev_knob("SAE_G8_NO_NTS") ? 1 : 0) |        \
+           (!dev_knob("SAE_G8_NO_AUX_NT") ? 2 : 0);
+    SAE_G8_TABLE(SAE_G8)
+#undef SAE_G8
+    default: return 0;
+  }
+}
+
+// ------------------------------------------------------------------------------- the plan
+// What nt_plan decides on: the call's shape and epilogue, the device's CU count and the value of
+// every dev knob of the dispatch (0 in the release library).  nt_facts reads the device and the
+// environment; the plan itself touches neither, so a shape plans the same with and without a device
+// of the same size (no device: 256 CUs).
+struct NtFacts {
+  int M, N, K;
+  int epilogue;   // SAE_EPI_* as passed
+  bool drop;      // sae_gemm_nt_gelu_dropout: the hidden dropout rides on SAE_EPI_GELU_GRAD
+  int cus;
+  int no_g8, bm256, variant, no_bn128, mul192, no_mul;   // SAE_NT_NO_G8, SAE_NT_BM256, SAE_NT_VARIANT,
+                                                         // SAE_G8_NO_BN128, SAE_G8_MUL192, SAE_G8_NO_MUL
+};
+
+NtFacts nt_facts(int M, int N, int K, int epilogue, bool drop) {
+  return NtFacts{M, N, K, epilogue, drop, device_cus(), dev_knob("SAE_NT_NO_G8"), dev_knob("SAE_NT_BM256"),
+                 dev_knob("SAE_NT_VARIANT"), dev_knob("SAE_G8_NO_BN128"), dev_knob("SAE_G8_MUL192"),
+                 dev_knob("SAE_G8_NO_MUL")};
 }
 
 // tile height of a gemm8 / gemm8x launch: 224 where 256-row tiles quantize worse onto the CUs --
 // cost = rounds of tiles over the CUs x rows per tile (M = 25,216 into 384 features: 198 tiles of
 // 256 rows, one round on 256 CUs with 58 idle, vs 226 of 224 rows; M = 18,464 into 768: 219 vs 249)
-int g8_pick_bm(int M, int N, int BN) {
-  if (dev_knob("SAE_NT_BM256")) return 256;
-  const long long G = device_cus(), tn = (N + BN - 1) / BN;
-  auto cost = [&](int bm) { return ((((long long)M + bm - 1) / bm * tn + G - 1) / G) * bm; };
+int g8_pick_bm(const NtFacts& f, int BN) {
+  if (f.bm256) return 256;
+  const long long G = f.cus, tn = (f.N + BN - 1) / BN;
+  auto cost = [&](int bm) { return ((((long long)f.M + bm - 1) / bm * tn + G - 1) / G) * bm; };
   return cost(224) < cost(256) ? 224 : 256;
-}
-
-// one persistent gemm8 launch (BM x BN tiles, one 8-wave workgroup per CU)
-template <int EPI, int BN, int BK, int NS, int BM, int WGM = 2, bool XW = false>
-int g8_launch_bm(const NtArgs& g0, hipStream_t st) {
-  const long long tiles = (long long)((g0.M + BM - 1) / BM) * ((g0.N + BN - 1) / BN);
-  NtArgs g = g0;
-  // epilogue stores non-temporal except for the gelu' multiply on 2 x 4 waves (whose 96-byte row segments then
-  // left L2 unmerged: 77 -> 102 MB written); DeiT-S step 8.02 -> 7.96 ms with every epilogue
-  // non-temporal, the plain / GELU launches faster and the multiply slower (profiles/r06z_g8_nts_ab.txt).
-  // The multiply's aux (gelu'(h)) tile loaded non-temporal: level in isolation, DeiT-S step
-  // 8.01 -> 7.85 ms (profiles/r06z4_g8_aux_nt_ab.txt)
-  g.nts = ((EPI != kEpiDGelu || WGM == 4) && !dev_knob("SAE_G8_NO_NTS") ? 1 : 0) | (!dev_knob("SAE_G8_NO_AUX_NT") ? 2 : 0);
-  return launch("gemm8_nt", gemm8_nt_kernel<EPI, BN, BK, NS, BM, WGM, XW>, std::min<long long>(tiles, device_cus()),
-                dim3(512), g8_lds_bytes<BN, BK, NS, WGM>(), st, g);
-}
-template <int EPI, int BN, int BK, int NS> int g8_launch(const NtArgs& g, hipStream_t st) {
-  // plain 192-wide tiles: whole-row epilogue stores through the shared row image (XW): QKV forward
-  // 32.9 -> 31.4 us, DeiT-S step -0.13 % (profiles/r06xw_g8_xw_ab.txt)
-  constexpr bool XW = EPI == kEpiNone && BN == 192;
-  return g8_pick_bm(g.M, g.N, BN) == 224 ? g8_launch_bm<EPI, BN, BK, NS, 224, 2, XW>(g, st)
-                                         : g8_launch_bm<EPI, BN, BK, NS, 256, 2, XW>(g, st);
 }
 
 // GELU forward at K < 768 (the epilogue's VALU work, which scales with the outputs, outweighs the
@@ -156,22 +290,14 @@ template <int EPI, int BN, int BK, int NS> int g8_launch(const NtArgs& g, hipStr
 // DeiT-S / CaiT-S FF Dense_0 (M 25,216 / 25,088 into 1,536): 5 rounds of 32 K outputs against 4 of
 // 43 K, 68.0 -> 63.8 us same box (profiles/r05ai_g8_bn128_ab.txt; the GELU' input gradient measured
 // level, so it keeps the 192-wide tiles)
-bool g8_gelu_bn128(int M, int N, int K) {
-  if (K >= 768 || N % 128 || dev_knob("SAE_G8_NO_BN128")) return false;
-  const long long G = device_cus();
-  const int bm = g8_pick_bm(M, N, 192);
+bool g8_gelu_bn128(const NtFacts& f) {
+  const int M = f.M, N = f.N;
+  if (f.K >= 768 || N % 128 || f.no_bn128) return false;
+  const long long G = f.cus;
+  const int bm = g8_pick_bm(f, 192);
   const long long c192 = (((long long)(M + bm - 1) / bm * ((N + 191) / 192) + G - 1) / G) * bm * 192;
   const long long c128 = (((long long)(M + 255) / 256 * (N / 128) + G - 1) / G) * 256 * 128;
   return c128 < c192;
-}
-
-// one gemm8x launch (BM x BN tiles, ping-pong wave groups, one tile per workgroup)
-template <int EPI, int BN, int BM> int g8x_launch_bm(const NtArgs& g, hipStream_t st) {
-  const long long tiles = (long long)((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-  return launch("gemm8x_nt", gemm8x_nt_kernel<EPI, BN, true, BM>, tiles, dim3(512), g8x_lds_bytes<BN, BM>(), st, g);
-}
-template <int EPI, int BN> int g8x_launch(const NtArgs& g, hipStream_t st) {
-  return g8_pick_bm(g.M, g.N, BN) == 224 ? g8x_launch_bm<EPI, BN, 224>(g, st) : g8x_launch_bm<EPI, BN, 256>(g, st);
 }
 
 // Kernel choice for sae_gemm_nt (round 5: a rule on tile fill and reduction depth instead of the
@@ -187,7 +313,8 @@ template <int EPI, int BN> int g8x_launch(const NtArgs& g, hipStream_t st) {
 //           inner 24 / 40 and their FF widths), the GELU' epilogue beyond K = 384 (its 256-token
 //           tile), N not a multiple of 192 or 256.
 // Both persistent kernels need M >= 4096 (enough tiles to fill the CUs) and K % 64 == 0.
-bool g8x_route(int M, int N, int K, int epilogue) {
+bool g8x_route(const NtFacts& f, int epilogue) {
+  const int M = f.M, N = f.N, K = f.K;
   if (epilogue == SAE_EPI_DGELU || K < 768 || K % 64 || M < 4096 || N % 256) return false;
   return N == 768 || N % 192 != 0;
 }
@@ -203,50 +330,67 @@ bool g8x_route(int M, int N, int K, int epilogue) {
 // (profiles/r04k_g8probe.txt, v53 vs rel)
 // Round 5: with the saved-gelu' multiply epilogue (SAE_EPI_MUL_AUX, `gp`) the GELU' epilogue no
 // longer bounds the deeper ViT-B input gradient either, so gemm8 takes it at every K.
-bool g8_route(int M, int N, int K, int epilogue, bool gp) {
+bool g8_route(const NtFacts& f, int epilogue, bool gp) {
+  const int M = f.M, N = f.N, K = f.K;
   if (N % 192 || K % 64 || K < 384 || M < 4096) return false;
-  return epilogue != SAE_EPI_DGELU || K == 384 || (gp && !dev_knob("SAE_G8_NO_MUL"));
+  return epilogue != SAE_EPI_DGELU || K == 384 || (gp && !f.no_mul);
 }
 
-// The one routing decision: sae_gemm_nt_route returns `route`, sae_gemm_nt launches by the whole plan.
-struct NtPlan {
-  int route;      // SAE_NT_ROUTE_*
-  int epilogue;   // SAE_EPI_NONE / GELU / DGELU: the gelu' forms run on the GELU / GELU' kernels ...
-  bool gp;        // ... with the saved operand gelu'(h)
-  bool bn128;     // gemm8: 256 x 128 tiles on 4 x 2 waves
-  bool tall;      // 128-row kernel: 256-token tiles
-  bool shallow;   // 128-row kernel: 32-deep stages
-};
-NtPlan nt_plan(int M, int N, int K, int epilogue) {
-  NtPlan p = {};
-  p.gp = epilogue >= SAE_EPI_GELU_GRAD;
-  p.epilogue = p.gp ? epilogue - 2 : epilogue;
-  const bool g8 = !dev_knob("SAE_NT_NO_G8");
-  if (g8 && g8x_route(M, N, K, p.epilogue)) {
-    p.route = SAE_NT_ROUTE_GEMM8X;
-  } else if (g8 && g8_route(M, N, K, p.epilogue, p.gp)) {
-    p.route = SAE_NT_ROUTE_GEMM8;
+// The one routing decision: sae_gemm_nt_route and sae_gemm_nt_instance report it, sae_gemm_nt,
+// sae_gemm_nt_gelu_dropout launch it.  Pure: no HIP call, no pointer, no environment.  Refuses
+// what no row takes.
+int nt_plan(const NtFacts& f, Inst* row) {
+  using I = Inst;
+  const int M = f.M, N = f.N, K = f.K;
+  if (M < 1 || N < 1 || K < 1) return fail(SAE_EINVAL, "gemm_nt: M/N/K must be >= 1 (got %d/%d/%d)", M, N, K);
+  if (K % 8 || N % 8) return fail(SAE_EUNSUPPORTED, "gemm_nt: K (%d) and N (%d) must be multiples of 8", K, N);
+  if (f.epilogue < SAE_EPI_NONE || f.epilogue > SAE_EPI_MUL_AUX)
+    return fail(SAE_EINVAL, "gemm_nt: unknown epilogue %d", f.epilogue);
+  if (f.drop && f.epilogue != SAE_EPI_GELU_GRAD)
+    return fail(SAE_EINVAL, "gemm_nt: dropout rides on the SAE_EPI_GELU_GRAD epilogue only (got %d)", f.epilogue);
+  // the gelu' forms run on the GELU / GELU' kernels with the saved operand gelu'(h) (NtArgs.gp)
+  const bool gp = f.epilogue >= SAE_EPI_GELU_GRAD;
+  const int epi = gp ? f.epilogue - 2 : f.epilogue;   // SAE_EPI_NONE / GELU / DGELU
+  const int e = f.drop ? kEpiGeluDrop : epi;          // the rows' EPI column: plain, gelu, dgelu, gelu_drop
+  if (!f.no_g8 && g8x_route(f, epi)) {
+    static const I rows[2][4] = {
+        {I::g8x_bm224_plain, I::g8x_bm224_gelu, I::count, I::g8x_bm224_gelu_drop},
+        {I::g8x_bm256_plain, I::g8x_bm256_gelu, I::count, I::g8x_bm256_gelu_drop}};
+    *row = rows[g8_pick_bm(f, 256) == 256][e];
+  } else if (!f.no_g8 && g8_route(f, epi, gp)) {
     // GELU on 4 x 2 waves (64 x 64 wave tiles): whole 128-byte output lines per wave row segment --
     // writes 172 -> 155 MB (= algorithmic), 57.1 -> 54.8 us at DeiT-S (profiles/r06w4_g8_wgm4_ab.txt);
     // the gelu' multiply on the same 256 x 128 tiles and 4 x 2 waves (whole-line stores, now also
     // non-temporal): 59.5 -> 53.8 us at DeiT-S, reads 128 -> 111 MB (profiles/r06m128_g8_mul_ab.txt)
-    p.bn128 = (p.epilogue == SAE_EPI_GELU || (p.epilogue == SAE_EPI_DGELU && !dev_knob("SAE_G8_MUL192"))) &&
-              g8_gelu_bn128(M, N, K);
+    static const I bn128[4] = {I::count, I::g8_128_wgm4_gelu, I::g8_128_wgm4_dgelu, I::g8_128_wgm4_gelu_drop};
+    static const I bn192[2][4] = {
+        {I::g8_192_bm224_plain, I::g8_192_bm224_gelu, I::g8_192_bm224_dgelu, I::g8_192_bm224_gelu_drop},
+        {I::g8_192_bm256_plain, I::g8_192_bm256_gelu, I::g8_192_bm256_dgelu, I::g8_192_bm256_gelu_drop}};
+    const bool may128 = epi == SAE_EPI_GELU || (epi == SAE_EPI_DGELU && !f.mul192);
+    *row = may128 && g8_gelu_bn128(f) ? bn128[e] : bn192[g8_pick_bm(f, 192) == 256][e];
   } else {
-    p.route = K % kNtK ? SAE_NT_ROUTE_TILE128_KTAIL : SAE_NT_ROUTE_TILE128;
+    // [loader][EPI]: the shallow and the tall tiles have no plain row
+    static const I rows[4][4] = {
+        {I::nt128_k64_plain, I::nt128_k64_gelu, I::nt128_k64_dgelu, I::nt128_k64_gelu_drop},
+        {I::count, I::nt128_k32_gelu, I::nt128_k32_dgelu, I::nt128_k32_gelu_drop},
+        {I::count, I::nt128_tall_gelu, I::nt128_tall_dgelu, I::nt128_tall_gelu_drop},
+        {I::nt128_ktail_plain, I::nt128_ktail_gelu, I::nt128_ktail_dgelu, I::nt128_ktail_gelu_drop}};
     // tile height: 256 tokens for the GELU / GELU' epilogue GEMMs at K >= 768 (the ViT-B FF block:
     // the epilogue's VALU work per output is amortised over twice the MFMA work per tile;
     // tools/nt_probe.py at M 36928 K 768 N 3072: GELU 512 -> 634, GELU' 548 -> 609 TF/s) when that
     // still gives >= 2 tiles per CU; 128 otherwise (plain GEMMs: no gain, profiles/r03n_nt_probe.txt)
-    p.tall = p.epilogue != SAE_EPI_NONE && K >= 768 && (long long)((M + 255) / 256) * ((N + kNtT - 1) / kNtT) >= 512;
-    if (const int ntv = dev_knob("SAE_NT_VARIANT")) p.tall = ntv == 2;
+    const bool fused = epi != SAE_EPI_NONE;
+    bool tall = fused && K >= 768 && (long long)((M + 255) / 256) * ((N + kNtT - 1) / kNtT) >= 512;
+    if (f.variant) tall = fused && f.variant == 2;
     // stage depth: the GELU / GELU' epilogue GEMMs at reduction depth <= 384 (DeiT-S / CaiT FF
     // block) run 32-deep stages (32 KiB of LDS: 3-4 workgroups per CU, so one tile's epilogue VALU
     // overlaps other tiles' MFMAs; same-box step A/B 9.19 -> 9.10 ms); deeper reductions (ViT-B,
     // K 768) and the plain GEMM keep 64-deep stages (2 workgroups per CU), which are faster there
-    p.shallow = p.epilogue != SAE_EPI_NONE && K <= 384;
+    const bool shallow = fused && K <= 384;
+    // K-tail instances (K % 8 == 0): 64-deep stages, the last one partial
+    *row = rows[K % kNtK ? 3 : tall ? 2 : shallow ? 1 : 0][e];
   }
-  return p;
+  return SAE_OK;
 }
 
 // ------------------------------------------------------------------------ patch embedding
@@ -290,11 +434,6 @@ int patch_geom(const sae_patch_desc* d, PatchGeom* g, int* M, int* K) {
   *M = (int)(L * d->batch);
   *K = (int)k;
   return 0;
-}
-
-template <bool HWCN, bool F32> int patch_fwd_launch(hipStream_t st, const NtArgs& g, long long grid) {
-  return launch("patch_embed_fwd", gemm_nt_kernel<kEpiNone, NtPatchA<HWCN, F32>>, grid, dim3(256), 4 * kNtT * kNtK * 2,
-                st, g);
 }
 
 template <bool HWCN, bool F32> int patch_dw_launch(hipStream_t st, const DwArgs& a) {
@@ -388,26 +527,38 @@ int sae_gemm_f32(void* stream, int32_t M, int32_t N, int32_t K, const float* a, 
 }
 
 int sae_gemm_nt_route(int32_t M, int32_t N, int32_t K, int32_t epilogue) {
-  if (M < 1 || N < 1 || K < 1 || K % 8 || N % 8 || epilogue < SAE_EPI_NONE || epilogue > SAE_EPI_MUL_AUX)
-    return SAE_NT_ROUTE_NONE;
-  return nt_plan(M, N, K, epilogue).route;
+  Inst row;
+  return nt_plan(nt_facts(M, N, K, epilogue, false), &row) ? SAE_NT_ROUTE_NONE : inst_route(row);
 }
 
-// drop != nullptr (epilogue SAE_EPI_GELU_GRAD): the kEpiGeluDrop instance of the kernel nt_plan routes
-// the plain call to -- same validation, same shape envelope, same route
+// host-only: the row sae_gemm_nt (dropout != 0: sae_gemm_nt_gelu_dropout) launches, by name
+const char* sae_gemm_nt_instance(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t dropout) {
+  Inst row;
+  if (nt_plan(nt_facts(M, N, K, epilogue, dropout != 0), &row)) return nullptr;
+  ok();
+  return inst_name(row);
+}
+
+// row `index` of the three tables, in table order (the tests hold a pin against every name)
+const char* sae_gemm_nt_instance_name(int32_t index) {
+  return index >= 0 && index < (int)Inst::count ? inst_name((Inst)index) : nullptr;
+}
+
+// plan, validate the operands, fill, launch.  drop != nullptr (epilogue SAE_EPI_GELU_GRAD): the
+// _gelu_drop row of the kernel nt_plan routes the plain call to -- same validation, same shape
+// envelope, same route
 static int gemm_nt_impl(void* stream, int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* bt,
                         int64_t ldb, const float* bias, void* c, int64_t ldc, int32_t epilogue, const void* aux,
                         int64_t ldaux, void* c2, const DropRows* drop) {
-  if (M < 1 || N < 1 || K < 1) return fail(SAE_EINVAL, "gemm_nt: M/N/K must be >= 1 (got %d/%d/%d)", M, N, K);
-  if (K % 8 || N % 8) return fail(SAE_EUNSUPPORTED, "gemm_nt: K (%d) and N (%d) must be multiples of 8", K, N);
+  const NtFacts f = nt_facts(M, N, K, epilogue, drop != nullptr);
+  Inst row;
+  if (int rc = nt_plan(f, &row)) return rc;
   if (lda < K || ldb < K || ldc < N || lda % 8 || ldb % 8 || ldc % 8)
     return fail(SAE_EINVAL, "gemm_nt: bad leading dimensions lda %lld ldb %lld ldc %lld", (long long)lda,
                 (long long)ldb, (long long)ldc);
   if (!a || !bt || !c) return fail(SAE_EINVAL, "gemm_nt: a/bt/c must be non-NULL");
-  if (epilogue < SAE_EPI_NONE || epilogue > SAE_EPI_MUL_AUX)
-    return fail(SAE_EINVAL, "gemm_nt: unknown epilogue %d", epilogue);
-  const NtPlan p = nt_plan(M, N, K, epilogue);
-  epilogue = p.epilogue;
+  const bool gp = epilogue >= SAE_EPI_GELU_GRAD;   // the gelu' forms: the GELU / GELU' checks and kernels
+  if (gp) epilogue -= 2;
   if (epilogue == SAE_EPI_GELU && !c2) return fail(SAE_EINVAL, "gemm_nt: the GELU epilogue needs c2 (pre-activation out)");
   if (epilogue == SAE_EPI_DGELU && (!aux || ldaux < N || ldaux % 8 || bias))
     return fail(SAE_EINVAL, "gemm_nt: the GELU-derivative epilogue needs aux (ldaux >= N, multiple of 8) and no bias");
@@ -421,7 +572,8 @@ static int gemm_nt_impl(void* stream, int32_t M, int32_t N, int32_t K, const voi
   g.bt = reinterpret_cast<const __bf16*>(bt);
   g.bias = bias;
   g.aux = reinterpret_cast<const __bf16*>(aux);
-  g.gp = p.gp ? 1 : 0;
+  g.gp = gp ? 1 : 0;
+  g.nts = g8_nts(row);
   g.c = reinterpret_cast<__bf16*>(c);
   g.c2 = reinterpret_cast<__bf16*>(c2);
   g.M = M;
@@ -431,36 +583,8 @@ static int gemm_nt_impl(void* stream, int32_t M, int32_t N, int32_t K, const voi
   g.ldb = ldb;
   g.ldc = ldc;
   g.ldaux = ldaux;
-  hipStream_t st = (hipStream_t)stream;
-  if (drop) {
-    g.drop = *drop;
-    if (p.route == SAE_NT_ROUTE_GEMM8X) return g8x_launch<kEpiGeluDrop, 256>(g, st);
-    if (p.route == SAE_NT_ROUTE_GEMM8)
-      return p.bn128 ? g8_launch_bm<kEpiGeluDrop, 128, 64, 2, 256, 4>(g, st) : g8_launch<kEpiGeluDrop, 192, 64, 2>(g, st);
-    epilogue = kEpiGeluDrop;   // the 128-row kernel, tile shape by the plan below
-  }
-  if (p.route == SAE_NT_ROUTE_GEMM8X)
-    return epilogue == SAE_EPI_NONE ? g8x_launch<kEpiNone, 256>(g, st) : g8x_launch<kEpiGelu, 256>(g, st);
-  if (p.route == SAE_NT_ROUTE_GEMM8) {
-    if (p.bn128)
-      return epilogue == SAE_EPI_GELU ? g8_launch_bm<kEpiGelu, 128, 64, 2, 256, 4>(g, st)
-                                      : g8_launch_bm<kEpiDGelu, 128, 64, 2, 256, 4>(g, st);
-    return epilogue == SAE_EPI_NONE   ? g8_launch<kEpiNone, 192, 64, 2>(g, st)
-           : epilogue == SAE_EPI_GELU ? g8_launch<kEpiGelu, 192, 64, 2>(g, st)
-                                      : g8_launch<kEpiDGelu, 192, 64, 2>(g, st);
-  }
-  const long long tn = (N + kNtT - 1) / kNtT;
-  const long long grid128 = (long long)((M + kNtT - 1) / kNtT) * tn;
-  // every launch below uses 128-row tiles (grid128) or taller ones (fewer workgroups)
-  if (grid128 >= (1LL << 31)) return fail(SAE_EUNSUPPORTED, "gemm_nt: grid too large");
-  // K-tail instances (K % 8 == 0): 64-deep stages, the last one partial
-  if (p.route == SAE_NT_ROUTE_TILE128_KTAIL) return nt_launch_epi<NtRowAT<64, 128, true>>(epilogue, g, grid128, st);
-  if (p.tall) return nt_launch_epi<NtRowAT<32, 256>>(epilogue, g, (long long)((M + 255) / 256) * tn, st);
-  if (p.shallow)
-    return epilogue == kEpiGeluDrop  ? nt_launch<kEpiGeluDrop, NtRowAT<32>>(g, grid128, st)
-           : epilogue == SAE_EPI_GELU ? nt_launch<kEpiGelu, NtRowAT<32>>(g, grid128, st)
-                                      : nt_launch<kEpiDGelu, NtRowAT<32>>(g, grid128, st);
-  return nt_launch_epi<NtRowAT<64>>(epilogue, g, grid128, st);
+  if (drop) g.drop = *drop;
+  return run_inst(row, (hipStream_t)stream, g, f.cus);
 }
 
 int sae_gemm_nt(void* stream, int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* bt,
@@ -497,11 +621,9 @@ int sae_patch_embed_fwd(void* stream, const sae_patch_desc* d, const void* image
   g.K = K;
   g.ldb = K;
   g.ldc = d->embed;
-  const long long grid = (long long)((M + kNtT - 1) / kNtT) * ((d->embed + kNtT - 1) / kNtT);
-  hipStream_t st = (hipStream_t)stream;
-  const bool hwcn = d->layout == SAE_LAYOUT_HWCN, f32 = d->dtype == SAE_DTYPE_F32;
-  return hwcn ? (f32 ? patch_fwd_launch<true, true>(st, g, grid) : patch_fwd_launch<true, false>(st, g, grid))
-              : (f32 ? patch_fwd_launch<false, true>(st, g, grid) : patch_fwd_launch<false, false>(st, g, grid));
+  static const Inst rows[2][2] = {{Inst::patch_nhwc_bf16, Inst::patch_nhwc_f32},
+                                  {Inst::patch_hwcn_bf16, Inst::patch_hwcn_f32}};
+  return run_inst(rows[d->layout == SAE_LAYOUT_HWCN][d->dtype == SAE_DTYPE_F32], (hipStream_t)stream, g);
 }
 
 int sae_patch_gather(void* stream, const sae_patch_desc* d, const void* images, void* patches) {

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _gemm_rows as G
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [  # (M, K, N)
@@ -345,3 +347,59 @@ def test_gemm_nt_gelu_grad_pair(dev, M, K, N):
     # and against the GELU' epilogue from h: the one extra bf16 rounding of gelu'
     dh_ref = ops.gemm_nt(a2, bt2, None, ops.EPI_DGELU, aux=h)
     assert _rel(dh, dh_ref.float()) <= 2e-2
+
+
+# One call per row of gemm.hip's instance tables (tests/_gemm_rows.py: the pins of the CPU routing test):
+# the query names the row, so the call below runs that instance, checked the way this file and
+# tests/test_gpu_dropout_rows.py check its epilogue.
+@pytest.mark.parametrize("M,K,N,epi,drop,name", G.NT_ROWS)
+def test_gemm_nt_every_row(dev, M, K, N, epi, drop, name):
+    import sae_vision_amd.ops as ops
+    from sae_vision_amd import _lib as L
+    lib = L.load()
+    assert G.instance(lib, M, K, N, epi, drop) == name
+    assert lib.sae_gemm_nt_route(M, N, K, epi) == G.route_of(name)
+    a, bt, b = _inputs(dev, M, K, N, 7 * M + K + N)
+    ref = a.double() @ bt.double().t()
+    if drop:                                         # test_gelu_gemm_dropout
+        from test_gpu_dropout_rows import _gelu64, _keep, _rng
+        from _util import TOL
+        rate, sid = 0.25, 5
+        c, c2 = ops.gemm_nt(a, bt, b, ops.EPI_GELU_GRAD, drop=(rate, _rng(dev).state, sid))
+        keep, pk = _keep(dev, M, N, rate, sid=sid)
+        assert bool((c[keep == 0] == 0).all()) and bool((c2[keep == 0] == 0).all())
+        assert float((c2[keep == 1] != 0).double().mean()) > 0.99
+        gelu, dgelu = _gelu64((ref + b.double()).to(torch.bfloat16).double())
+        assert _rel(c, gelu * keep / pk) <= TOL["bf16"]
+        assert _rel(c2, dgelu * keep / pk) <= TOL["bf16"]
+    elif epi == ops.EPI_NONE:                        # test_gemm_nt_generalised_routes
+        c = ops.gemm_nt(a, bt, b)
+        assert _rel(c, ref + b.double()) <= 1e-2
+        assert torch.equal(ops.gemm_nt(a, bt, b), c)
+    elif epi == ops.EPI_GELU:
+        y, h = ops.gemm_nt(a, bt, b, ops.EPI_GELU)
+        assert _rel(h, ref + b.double()) <= 1e-2
+        ref_y = F.gelu(h.float(), approximate="tanh")
+        assert float((y.float() - ref_y).abs().max()) <= 2 ** -7 * float(ref_y.abs().max())
+    elif epi == ops.EPI_GELU_GRAD:                   # test_gemm_nt_gelu_grad_pair, the forward side
+        y, g = ops.gemm_nt(a, bt, b, ops.EPI_GELU_GRAD)
+        y_ref, h = ops.gemm_nt(a, bt, b, ops.EPI_GELU)
+        assert torch.equal(y, y_ref)
+        hf = h.float().requires_grad_(True)
+        F.gelu(hf, approximate="tanh").sum().backward()
+        assert float((g.float() - hf.grad).abs().max()) <= 2 ** -8 * float(hf.grad.abs().max()) + 1e-6
+    else:
+        gen = torch.Generator(device=dev).manual_seed(5)
+        h = (torch.randn(M, N, device=dev, generator=gen) * 2).to(torch.bfloat16)
+        hf = h.float().requires_grad_(True)
+        da = ref.to(torch.bfloat16).float()
+        if epi == ops.EPI_DGELU:                     # test_gemm_nt_generalised_routes
+            dh = ops.gemm_nt(a, bt, None, ops.EPI_DGELU, aux=h)
+            F.gelu(hf, approximate="tanh").backward(da)
+            assert _rel(dh, hf.grad) <= 1e-2
+        else:                                        # test_gemm_nt_gelu_grad_pair, the input-gradient side
+            F.gelu(hf, approximate="tanh").sum().backward()
+            g = hf.grad.to(torch.bfloat16)
+            dh = ops.gemm_nt(a, bt, None, ops.EPI_MUL_AUX, aux=g)
+            assert _rel(dh, da * g.float()) <= 1e-2
+            assert _rel(dh, ops.gemm_nt(a, bt, None, ops.EPI_DGELU, aux=h).float()) <= 2e-2

@@ -8,6 +8,7 @@ HIP kernel for it.  The projections are attention.py:29-37,60-63 and the FF bloc
 The rocprofv3 step profiles confirm on the GPU that no library GEMM runs (profiles/)."""
 import pytest
 
+import _gemm_rows as G   # one pinned call per gemm_nt instance row, shared with tests/test_gpu_gemm_nt.py
 import sae_vision_amd.ops as ops
 from _layouts import desc as _desc, route as _route   # one way to build a descriptor, shared with the layout matrix
 from sae_vision_amd import _lib as L
@@ -98,6 +99,45 @@ def test_library_switch():
     finally:
         ops.GEMM_LIB = old
     assert ops.use_gemm_nt(768, 2304)
+
+
+# ``sae_gemm_nt_instance`` reports the row of gemm.hip's instance tables that nt_plan picks, by name
+# (tile height, tile width, stage depth, epilogue, dropout: what the four-value route does not tell).
+@pytest.mark.parametrize("M,K,N,epi,drop,want", G.NT_ROWS)
+def test_gemm_nt_instance(lib, M, K, N, epi, drop, want):
+    assert G.instance(lib, M, K, N, epi, drop) == want
+    assert lib.sae_gemm_nt_route(M, N, K, epi) == G.route_of(want)
+
+
+def test_every_gemm_nt_row_is_pinned(lib):
+    """The library's row list (by index, NULL past the end) against the pins: a new row needs one."""
+    rows = []
+    while (name := lib.sae_gemm_nt_instance_name(len(rows))) is not None:
+        rows.append(name.decode())
+    assert lib.sae_gemm_nt_instance_name(-1) is None
+    assert len(rows) == len(set(rows)) == 11 + 6 + 14 + 4
+    assert set(rows) - G.PATCH_ROWS == {want for *_, want in G.NT_ROWS}
+    assert G.PATCH_ROWS <= set(rows)
+
+
+def test_gemm_nt_instance_baseline_and_refusals(lib):
+    M_s, M_b = 128 * 197, 32 * 577
+    # DeiT-S: 226 tiles of 224 rows on the 384-feature outputs and the QKV forward, the FF pair on 256 x 128
+    assert G.instance(lib, M_s, 384, 384, G.NONE) == "g8_192_bm224_plain"
+    assert G.instance(lib, M_s, 384, 1152, G.NONE) == "g8_192_bm224_plain"
+    assert G.instance(lib, M_s, 384, 1536, G.GELU_GRAD) == "g8_128_wgm4_gelu"
+    assert G.instance(lib, M_s, 384, 1536, G.GELU_GRAD, 1) == "g8_128_wgm4_gelu_drop"
+    assert G.instance(lib, M_s, 384, 1536, G.MUL_AUX) == "g8_128_wgm4_dgelu"
+    # ViT-B@384: the 768-feature outputs on gemm8x, the GELU' epilogue from h on the tall 128-row tile
+    assert G.instance(lib, M_b, 3072, 768, G.NONE) == "g8x_bm224_plain"            # 249 tiles of 224 rows: one round
+    assert G.instance(lib, M_b, 768, 3072, G.DGELU) == "nt128_tall_dgelu"
+    assert G.instance(lib, M_b, 768, 3072, G.MUL_AUX) == "g8_192_bm256_dgelu"       # 5 rounds of 256 against 6 of 224
+    for args, text in (((1024, 12, 1000, 0, 0), "gemm_nt: K (12) and N (1000) must be multiples of 8"),
+                       ((0, 64, 64, 0, 0), "gemm_nt: M/N/K must be >= 1"),
+                       ((128, 64, 64, 5, 0), "gemm_nt: unknown epilogue 5"),
+                       ((128, 64, 64, G.GELU, 1), "gemm_nt: dropout rides on the SAE_EPI_GELU_GRAD epilogue only")):
+        assert G.instance(lib, *args) is None
+        assert lib.sae_last_error().decode().startswith(text)
 
 
 # ------------------------------------------------------------------ attention routing

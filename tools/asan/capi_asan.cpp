@@ -267,12 +267,52 @@ static void routes_agree() {
          "route: bad pass / form");
 }
 
+// sae_gemm_nt_instance names a row exactly when sae_gemm_nt / sae_gemm_nt_gelu_dropout get as far as
+// the launch, its table agrees with sae_gemm_nt_route, and the row list ends in NULL.
+static void gemm_rows_agree() {
+  void *a = fake(), *bt = fake(), *c = fake(), *c2 = fake(), *aux = fake();
+  const uint64_t* rng = static_cast<const uint64_t*>(fake());
+  auto launched = [](int rc) { return rc == SAE_EHIP || rc == SAE_OK; };
+  auto refused = [](int rc) { return rc == SAE_EINVAL || rc == SAE_EUNSUPPORTED; };
+  int rows = 0;
+  while (sae_gemm_nt_instance_name(rows)) ++rows;
+  expect(rows == 35 && !sae_gemm_nt_instance_name(-1) && !sae_gemm_nt_instance_name(rows + 1), "gemm_nt row list");
+  // the shapes tests/_gemm_rows.py pins, the training shapes, and refused ones (M 0, K 12, N 10)
+  for (int M : {0, 128, 130, 4000, 4096, 4100, 18464, 25216})
+    for (int K : {12, 40, 128, 384, 448, 768, 3072})
+      for (int N : {10, 64, 72, 136, 192, 384, 768, 1536, 2688, 3584, 4096})
+        for (int epi : {-1, SAE_EPI_NONE, SAE_EPI_GELU, SAE_EPI_DGELU, SAE_EPI_GELU_GRAD, SAE_EPI_MUL_AUX, 5})
+          for (int drop : {0, 1}) {
+            const char* row = sae_gemm_nt_instance(M, N, K, epi, drop);
+            const bool dgelu = epi == SAE_EPI_DGELU || epi == SAE_EPI_MUL_AUX;
+            int rc;
+            if (drop && epi != SAE_EPI_GELU_GRAD) {
+              expect(!row && std::strlen(sae_last_error()) > 0, "gemm_nt instance: dropout needs GELU_GRAD");
+              continue;
+            }
+            if (drop)
+              rc = sae_gemm_nt_gelu_dropout(nullptr, M, N, K, a, K, bt, K, nullptr, c, N, c2, 0.25f, rng, 3);
+            else
+              rc = sae_gemm_nt(nullptr, M, N, K, a, K, bt, K, nullptr, c, N, epi, dgelu ? aux : nullptr, dgelu ? N : 0,
+                               c2);
+            expect(row ? launched(rc) : refused(rc), "sae_gemm_nt_instance agrees with the entry point");
+            const int route = sae_gemm_nt_route(M, N, K, epi);
+            expect((row != nullptr) == (route != SAE_NT_ROUTE_NONE), "sae_gemm_nt_instance agrees with the route");
+            if (row)
+              expect((route == SAE_NT_ROUTE_GEMM8X) == !std::strncmp(row, "g8x_", 4) &&
+                         (route == SAE_NT_ROUTE_GEMM8) == !std::strncmp(row, "g8_", 3) &&
+                         (route == SAE_NT_ROUTE_TILE128_KTAIL) == !std::strncmp(row, "nt128_ktail_", 12),
+                     "row name and route name the same table");
+          }
+}
+
 int main() {
   std::mt19937 rng(1234);
   adamw_plans(rng);
   workspace_sizes();
   validation();
   routes_agree();
+  gemm_rows_agree();
   std::printf("capi_asan: %d checks, %d failed\n", g_checks, g_fail);
   return g_fail ? 1 : 0;
 }

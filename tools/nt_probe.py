@@ -3,9 +3,12 @@
 
     SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so python tools/nt_probe.py
 
-Needs the dev library (SAE_NT_VARIANT: 1 = 128-token tiles, 2 = 256-token tiles, 0 = the release
-policy; NT_VARIANTS picks them, the first is the bit-equality reference; NT_PROBE_SHAPES filters shapes).  Per shape: y = x W (fwd, bt = W^T), dX = dY W^T, and for the FF shapes the GELU
-and GELU' epilogues; each variant's output is checked bit-equal to the 128-token tile's.
+Needs the dev library (SAE_NT_VARIANT: 1 = 128-token tiles, 2 = 256-token tiles for the GELU, GELU'
+and dropout epilogues -- the plain GEMM has no 256-token instance, it measured no gain
+(profiles/r03n_nt_probe.txt), so its fwd / dX columns are the 128-token tile under every variant --
+0 = the release policy; NT_VARIANTS picks them, the first is the bit-equality reference;
+NT_PROBE_SHAPES filters shapes).  Per shape: y = x W (fwd, bt = W^T), dX = dY W^T, and for the FF
+shapes the GELU and GELU' epilogues; each variant's output is checked bit-equal to the 128-token tile's.
 """
 import os
 import sys
