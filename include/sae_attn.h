@@ -476,6 +476,53 @@ int sae_adamw_step_cast(void* stream, int64_t n_chunks, const sae_adamw_chunk* c
                         const sae_adamw_cast_tile* tiles, int32_t* step, float lr, float beta1, float beta2,
                         float eps, float weight_decay);
 
+/* The reference's optimizer chain around that update (train.py:22-27,214-220: optax.chain of
+   clip_by_global_norm(max_norm), scale_by_adam, additive_weight_decay, scale_by_schedule of
+   warmup_cosine_decay_schedule).  The two values that change every step live in device memory,
+   hyper = {lr_t, clip_scale, grad_norm, unused} (4 floats), so a captured graph replays with
+   this step's rate and this step's clip.
+
+   sae_adamw_prepare takes the place of the step-counter tick.  It
+     1. computes the global norm of the contiguous fp32 gradient buffer g[0..n): one workgroup
+        per SAE_ADAMW_NORM_SPAN elements writes one fp64 partial sum of squares to `workspace`
+        (sae_adamw_prepare_workspace_bytes(n) bytes, 8-byte aligned; squares and sums in fp64, no
+        atomics: two calls on the same data give the same bits), 16-byte loads when g is 16-byte
+        aligned, scalar loads otherwise;
+     2. in one workgroup adds the partials in a fixed order (SAE_ADAMW_PREPARE_PASS per pass) and
+        writes grad_norm = sqrt(sum) and clip_scale = grad_norm < max_norm ? 1 : max_norm / grad_norm
+        (a zero norm gives 1; a NaN norm gives NaN, an infinite one 0: nothing is skipped
+        silently; max_norm = +inf only monitors the norm);
+     3. writes lr_t = the schedule at count = *step, the number of updates already applied (as
+        optax counts), then increments *step.
+   With n == 0 and g == workspace == NULL step 1 is left out (grad_norm 0, clip_scale 1).
+   Schedules: SAE_LR_CONSTANT (lr_t = peak) and SAE_LR_WARMUP_COSINE, as optax composes it:
+     count < warmup_steps:  init + (peak - init) count / warmup_steps
+     otherwise, c = min(count - warmup_steps, D), D = decay_steps - warmup_steps, a = end / peak:
+                            peak ((1 - a) (1 + cos(pi c / D)) / 2 + a)
+   SAE_EINVAL: NULL schedule / step / hyper, n < 1 or a NULL g / workspace (unless all three are
+   0 / NULL), max_norm <= 0 or NaN, an unknown kind, peak <= 0 or not finite, warmup_steps < 0,
+   decay_steps <= warmup_steps, init / end negative or not finite.
+
+   sae_adamw_step_dev is sae_adamw_step (n_tiles == 0) / sae_adamw_step_cast without the tick, with
+   lr = hyper[0] and every gradient multiplied by hyper[1] (rounded to fp32) before the same
+   arithmetic; with clip_scale 1 its results are bit-identical to theirs.  Call it after
+   sae_adamw_prepare on the same stream. */
+#define SAE_ADAMW_NORM_SPAN 16384
+#define SAE_ADAMW_PREPARE_PASS 256
+#define SAE_LR_CONSTANT 0
+#define SAE_LR_WARMUP_COSINE 1
+typedef struct sae_lr_schedule {
+  int32_t kind;          /* SAE_LR_* */
+  float init, peak, end; /* SAE_LR_CONSTANT reads peak only */
+  int32_t warmup_steps, decay_steps;
+} sae_lr_schedule;
+size_t sae_adamw_prepare_workspace_bytes(int64_t n);
+int sae_adamw_prepare(void* stream, int64_t n, const float* g, float max_norm, const sae_lr_schedule* schedule,
+                      int32_t* step, void* workspace, float* hyper);
+int sae_adamw_step_dev(void* stream, int64_t n_chunks, const sae_adamw_chunk* chunks, int64_t n_tiles,
+                       const sae_adamw_cast_tile* tiles, const int32_t* step, const float* hyper, float beta1,
+                       float beta2, float eps, float weight_decay);
+
 /* Encoder input of ViT / DeiT (models/vit.py:82-85 class-token concatenate, vit.py:46 +
    position_embed.py:48 AddAbsPosEmbed), tokens bf16 [B][L][E] from the patch embedding, cls fp32
    [E], pos fp32 [L+1][E]:  x fp32 [B][L+1][E] = concat(cls, float(tokens)) + pos.  Backward:

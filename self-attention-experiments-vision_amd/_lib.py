@@ -109,6 +109,9 @@ _PROTOS = [
     ("sae_adamw_step", _i32, [_vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32]),
     ("sae_adamw_cast_plan", _i32, [_i32] + [_vp] * 11 + [_vp, _i64, _vp]),
     ("sae_adamw_step_cast", _i32, [_vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32]),
+    ("sae_adamw_prepare_workspace_bytes", _sz, [_i64]),
+    ("sae_adamw_prepare", _i32, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp]),
+    ("sae_adamw_step_dev", _i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _f32, _f32, _f32, _f32]),
     ("sae_tokens_fwd", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("sae_tokens_bwd", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("sae_smoothed_ce_fwd", _i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp]),
@@ -145,7 +148,16 @@ class AdamwCastTile(ctypes.Structure):
         [(f, ctypes.c_int32) for f in ("K", "N", "ld16", "ldT", "col0", "k0", "n0", "pad")]
 
 
+class LrSchedule(ctypes.Structure):
+    """Mirror of ``sae_lr_schedule`` (include/sae_attn.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("init", ctypes.c_float), ("peak", ctypes.c_float), ("end", ctypes.c_float),
+                ("warmup_steps", ctypes.c_int32), ("decay_steps", ctypes.c_int32)]
+
+
 SAE_ADAMW_CHUNK = 2048
+SAE_ADAMW_NORM_SPAN = 16384
+SAE_ADAMW_PREPARE_PASS = 256
+SAE_LR_CONSTANT, SAE_LR_WARMUP_COSINE = 0, 1
 
 
 class SaeError(RuntimeError):

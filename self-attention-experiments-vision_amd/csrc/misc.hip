@@ -496,6 +496,77 @@ int sae_adamw_step_cast(void* stream, int64_t n_chunks, const sae_adamw_chunk* c
                 step, lr, beta1, beta2, eps, weight_decay);
 }
 
+// ---- the reference's chain around the update: global-norm clip and learning-rate schedule
+static_assert(sizeof(sae_lr_schedule) == sizeof(AdamwSchedule) && SAE_ADAMW_NORM_SPAN == kAdamwNormSpan &&
+                  SAE_ADAMW_PREPARE_PASS == kAdamwPreparePass && SAE_LR_CONSTANT == 0,
+              "sae_lr_schedule mirrors AdamwSchedule");
+
+// x is a finite number >= lo (> lo if strict); +inf passes if inf_ok.  NaN is tested on the bits:
+// the library is compiled with -fno-honor-nans, under which a comparison may not refuse one.
+static bool adamw_arg_ok(float x, float lo, bool strict, bool inf_ok) {
+  uint32_t u;
+  memcpy(&u, &x, sizeof u);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return false;
+  if (!inf_ok && (u & 0x7fffffffu) == 0x7f800000u) return false;
+  return strict ? x > lo : x >= lo;
+}
+
+size_t sae_adamw_prepare_workspace_bytes(int64_t n) {
+  return n < 1 ? 0 : (size_t)((n + SAE_ADAMW_NORM_SPAN - 1) / SAE_ADAMW_NORM_SPAN) * sizeof(double);
+}
+
+int sae_adamw_prepare(void* stream, int64_t n, const float* g, float max_norm, const sae_lr_schedule* schedule,
+                      int32_t* step, void* workspace, float* hyper) {
+  if (!schedule || !step || !hyper) return fail(SAE_EINVAL, "adamw_prepare: NULL schedule / step / hyper");
+  const bool with_norm = n != 0 || g || workspace;   // n == 0 and both NULL: the schedule alone
+  if (with_norm && (n < 1 || !g || !workspace))
+    return fail(SAE_EINVAL, "adamw_prepare: the norm pass needs n >= 1 (%lld), g and workspace", (long long)n);
+  if (with_norm && (((uintptr_t)g & 3) || ((uintptr_t)workspace & 7)))
+    return fail(SAE_EINVAL, "adamw_prepare: g must be 4-byte and workspace 8-byte aligned");
+  if (!adamw_arg_ok(max_norm, 0.f, true, true))
+    return fail(SAE_EINVAL, "adamw_prepare: max_norm (%g) must be > 0 (+inf: no clip)", (double)max_norm);
+  const sae_lr_schedule& s = *schedule;
+  if (s.kind != SAE_LR_CONSTANT && s.kind != SAE_LR_WARMUP_COSINE)
+    return fail(SAE_EINVAL, "adamw_prepare: unknown schedule kind %d", s.kind);
+  if (!adamw_arg_ok(s.peak, 0.f, true, false))
+    return fail(SAE_EINVAL, "adamw_prepare: peak (%g) must be > 0 and finite", (double)s.peak);
+  if (s.kind == SAE_LR_WARMUP_COSINE) {
+    if (s.warmup_steps < 0) return fail(SAE_EINVAL, "adamw_prepare: warmup_steps (%d) must be >= 0", s.warmup_steps);
+    if (s.decay_steps <= s.warmup_steps)
+      return fail(SAE_EINVAL, "adamw_prepare: decay_steps (%d) must be > warmup_steps (%d)", s.decay_steps,
+                  s.warmup_steps);
+    if (!adamw_arg_ok(s.init, 0.f, false, false) || !adamw_arg_ok(s.end, 0.f, false, false))
+      return fail(SAE_EINVAL, "adamw_prepare: init (%g) and end (%g) must be >= 0 and finite", (double)s.init,
+                  (double)s.end);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long long parts = with_norm ? (long long)((n + SAE_ADAMW_NORM_SPAN - 1) / SAE_ADAMW_NORM_SPAN) : 0;
+  if (parts > 0x7fffffffLL) return fail(SAE_EUNSUPPORTED, "adamw_prepare: n %lld too large", (long long)n);
+  double* partial = reinterpret_cast<double*>(workspace);
+  if (with_norm)
+    if (int rc = launch("adamw_sumsq", adamw_sumsq_kernel, parts, dim3(256), 0, st, g, (long long)n, partial)) return rc;
+  AdamwSchedule k;
+  memcpy(&k, &s, sizeof k);
+  return launch("adamw_prepare", adamw_prepare_kernel, 1LL, dim3(256), 0, st, (const double*)partial, (int)parts,
+                max_norm, k, step, hyper);
+}
+
+int sae_adamw_step_dev(void* stream, int64_t n_chunks, const sae_adamw_chunk* chunks, int64_t n_tiles,
+                       const sae_adamw_cast_tile* tiles, const int32_t* step, const float* hyper, float beta1,
+                       float beta2, float eps, float weight_decay) {
+  if (n_chunks < 0 || n_tiles < 0 || n_chunks + n_tiles >= (1LL << 31) || (n_chunks > 0 && !chunks) ||
+      (n_tiles > 0 && !tiles) || !step || !hyper)
+    return fail(SAE_EINVAL, "adamw_step_dev: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_chunks + n_tiles == 0) return ok();
+  if (n_tiles == 0)
+    return launch("adamw_dev", adamw_dev_kernel, (long long)n_chunks, dim3(256), 0, st,
+                  reinterpret_cast<const AdamwChunk*>(chunks), step, hyper, beta1, beta2, eps, weight_decay);
+  return launch("adamw_cast_dev", adamw_cast_dev_kernel, (long long)(n_chunks + n_tiles), dim3(256), 0, st,
+                reinterpret_cast<const AdamwChunk*>(chunks), (int)n_chunks, reinterpret_cast<const AdamwCastTile*>(tiles),
+                step, hyper, beta1, beta2, eps, weight_decay);
+}
+
 // ------------------------------------------------------------------------ stream utilities
 // bench.py --emulate-rccl: workgroups that hold their CU's slots (waves, LDS) for `ticks` of the
 // 100 MHz real-time counter while sleeping -- the CU footprint of an RCCL ring channel

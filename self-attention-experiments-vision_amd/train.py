@@ -22,19 +22,68 @@ process group).  ``SAE_WORLD1_RCCL=1`` (bench.py ``--world1-rccl``) creates a wo
 group so the overlapped collective path runs on a one-GPU box.
 
 Loss: one-hot -> optax.smooth_labels(0.1) -> softmax cross-entropy, mean (train.py:83-92).
-Optimizer: Adam + decoupled weight decay 1e-4, lr 5e-4 * batch/512 (train.py:25-27,229-233;
-constant schedule: the warmup-cosine value does not change the work per step).
+Optimizer: the reference's chain (train.py:22-27,214-220): clip_by_global_norm(``clip_grad``),
+Adam, decoupled weight decay 1e-4, scale by the schedule.  ``lr_schedule=None`` keeps the constant
+rate 5e-4 * batch/512 and ``clip_grad=None`` no clip (the defaults, which launch exactly what a step
+without the feature launched); a ``WarmupCosine`` (``reference_schedule`` builds the reference's) and
+a clip norm put the learning rate and the clip factor into device memory, computed per step by
+``sae_adamw_prepare`` (csrc/adamw.h), so the captured graph replays with each step's own values.
 """
 from __future__ import annotations
 
+import math
 import os
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-__all__ = ["smoothed_cross_entropy", "TrainStep", "init_distributed", "FusedAdamW"]
+__all__ = ["smoothed_cross_entropy", "TrainStep", "init_distributed", "FusedAdamW", "WarmupCosine",
+           "reference_schedule"]
+
+
+@dataclass(frozen=True)
+class WarmupCosine:
+    """optax.warmup_cosine_decay_schedule (reference train.py:215-220): linear from ``init_value``
+    to ``peak_value`` over ``warmup_steps`` updates, then a cosine from ``peak_value`` to
+    ``end_value`` that ends at update ``decay_steps`` (counted from 0, warm-up included) and stays
+    there.  ``value(count)``: the rate of the update after ``count`` updates, as optax counts."""
+    init_value: float
+    peak_value: float
+    warmup_steps: int
+    decay_steps: int
+    end_value: float = 0.0
+
+    def __post_init__(self):
+        if not (self.peak_value > 0 and math.isfinite(self.peak_value)):
+            raise ValueError(f"WarmupCosine: peak_value ({self.peak_value}) must be > 0 and finite")
+        if self.warmup_steps < 0 or self.decay_steps <= self.warmup_steps:
+            raise ValueError(f"WarmupCosine: need 0 <= warmup_steps ({self.warmup_steps}) < decay_steps "
+                             f"({self.decay_steps})")
+        if not (0 <= self.init_value < math.inf and 0 <= self.end_value < math.inf):
+            raise ValueError("WarmupCosine: init_value and end_value must be >= 0 and finite")
+
+    def value(self, count: int) -> float:
+        if count < self.warmup_steps:
+            return self.init_value + (self.peak_value - self.init_value) * count / self.warmup_steps
+        D = self.decay_steps - self.warmup_steps
+        c = min(count - self.warmup_steps, D)
+        alpha = self.end_value / self.peak_value
+        return self.peak_value * ((1 - alpha) * 0.5 * (1 + math.cos(math.pi * c / D)) + alpha)
+
+
+def reference_schedule(lr: float, global_batch: int, steps_per_epoch: int) -> WarmupCosine:
+    """The reference's schedule (train.py:214-220): from 0 to lr * batch/512 over 5 epochs, cosine
+    to 1e-5 at epoch 30."""
+    return WarmupCosine(0.0, lr * (global_batch / 512), 5 * steps_per_epoch, 30 * steps_per_epoch, 1e-5)
+
+
+def _check_clip(clip_grad):
+    if clip_grad is not None and not float(clip_grad) > 0:   # (NaN included)
+        raise ValueError(f"clip_grad ({clip_grad}) must be > 0 (None: no clip)")
+    return None if clip_grad is None else float(clip_grad)
 
 
 def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.1) -> torch.Tensor:
@@ -124,10 +173,19 @@ class FusedAdamW:
     groups; each kernel a whole parameter, possibly reshaped) whose bf16 compute copies the
     update writes as it goes (``sae_adamw_step_cast``): the forward then reads persistent copies
     (``ops.register_persistent_casts``) instead of casting every weight at its start.  Parameter
-    values are bit-identical either way."""
+    values are bit-identical either way.
+
+    ``clip_grad`` (optax.clip_by_global_norm's max_norm), ``lr_schedule`` (a ``WarmupCosine``; None:
+    the constant ``lr``) and ``monitor_norm`` (the norm without a clip): with any of them ``step()``
+    is ``sae_adamw_prepare`` (global norm of the WHOLE flat buffer, clip factor, this step's rate,
+    counter tick) followed by ``sae_adamw_step_dev`` on the current stream, so the norm always sits
+    directly before the update wherever ``step()`` is captured.  ``lr_now`` and ``grad_norm`` are
+    device views of the ``hyper`` buffer those kernels share (no sync; None without the feature).
+    With all three at their defaults ``step()`` makes exactly the calls it made without them."""
 
     def __init__(self, params, flat_grad: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, cast_groups=None):
+                 weight_decay: float = 0.0, cast_groups=None, clip_grad: Optional[float] = None,
+                 lr_schedule: Optional[WarmupCosine] = None, monitor_norm: bool = False):
         import ctypes
         from . import _lib as L
         from . import ops
@@ -138,6 +196,25 @@ class FusedAdamW:
         self.m = torch.zeros_like(flat_grad)
         self.v = torch.zeros_like(flat_grad)
         self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.clip_grad, self.lr_schedule = _check_clip(clip_grad), lr_schedule
+        if lr_schedule is not None and not isinstance(lr_schedule, WarmupCosine):
+            raise TypeError("FusedAdamW: lr_schedule must be a WarmupCosine or None")
+        self.hyper = None   # {lr_t, clip_scale, grad_norm, -} on the device, written by sae_adamw_prepare
+        if self.clip_grad is not None or lr_schedule is not None or monitor_norm:
+            if flat_grad.dtype != torch.float32 or not flat_grad.is_contiguous() or flat_grad.dim() != 1:
+                raise ValueError("FusedAdamW: the flat gradient buffer must be 1-D contiguous fp32")
+            self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)
+            s = lr_schedule
+            self._sched = (L.LrSchedule(L.SAE_LR_CONSTANT, 0.0, self.lr, 0.0, 0, 0) if s is None else
+                           L.LrSchedule(L.SAE_LR_WARMUP_COSINE, s.init_value, s.peak_value, s.end_value,
+                                        int(s.warmup_steps), int(s.decay_steps)))
+            # the norm runs over the whole flat buffer, alignment padding included: the padding is
+            # zero when the buffer is built and nothing ever writes it (TrainStep, flat_layout)
+            self._norm_of, self._norm_ws = None, None
+            if self.clip_grad is not None or monitor_norm:
+                self._norm_of = flat_grad
+                nbytes = int(self.lib.sae_adamw_prepare_workspace_bytes(flat_grad.numel()))
+                self._norm_ws = torch.zeros(nbytes // 8, dtype=torch.float64, device=dev)
         # copies an earlier optimizer over these parameters registered would go stale under this
         # one (it updates the weights through raw pointers): they stop being served
         ops.release_persistent_casts(self.params)
@@ -217,11 +294,33 @@ class FusedAdamW:
             import weakref
             weakref.finalize(self, ops.unregister_persistent_casts, list(self.cast_groups), self._owner)
 
+    @property
+    def lr_now(self):
+        """The rate the last update used (0-d device view; None without clip / schedule / monitor)."""
+        return None if self.hyper is None else self.hyper[0]
+
+    @property
+    def grad_norm(self):
+        """The global gradient norm the last update saw, before clipping (0-d device view; 0 unless
+        ``clip_grad`` or ``monitor_norm`` asked for the norm pass)."""
+        return None if self.hyper is None else self.hyper[2]
+
     def step(self):
+        import ctypes
         from . import _lib as L
         b1, b2 = self.betas
         st = torch.cuda.current_stream(self.m.device).cuda_stream
-        if self.n_tiles:
+        if self.hyper is not None:
+            g = self._norm_of
+            L.check(self.lib.sae_adamw_prepare(
+                st, 0 if g is None else g.numel(), None if g is None else g.data_ptr(),
+                math.inf if self.clip_grad is None else self.clip_grad, ctypes.byref(self._sched),
+                self.step_count.data_ptr(), None if g is None else self._norm_ws.data_ptr(), self.hyper.data_ptr()))
+            L.check(self.lib.sae_adamw_step_dev(st, self.n_chunks, self.table.data_ptr(), self.n_tiles,
+                                                self.tiles.data_ptr() if self.n_tiles else None,
+                                                self.step_count.data_ptr(), self.hyper.data_ptr(), b1, b2, self.eps,
+                                                self.weight_decay))
+        elif self.n_tiles:
             L.check(self.lib.sae_adamw_step_cast(st, self.n_chunks, self.table.data_ptr(), self.n_tiles,
                                                  self.tiles.data_ptr(), self.step_count.data_ptr(), self.lr, b1, b2,
                                                  self.eps, self.weight_decay))
@@ -252,7 +351,7 @@ class FusedAdamW:
             self.cast_groups = []
 
     def state_tensors(self):
-        return [self.m, self.v, self.step_count]
+        return [self.m, self.v, self.step_count] + ([] if self.hyper is None else [self.hyper])
 
 
 class TrainStep:
@@ -261,13 +360,27 @@ class TrainStep:
 
     graph=True (GPU): the whole step is one HIP graph (collective "overlap" or "none"); with
     ``two_graphs=True`` (collective "between") or the gloo rehearsal ("host"): graph 1 = forward +
-    loss + backward, the bucket all-reduces, graph 2 = AdamW."""
+    loss + backward, the bucket all-reduces, graph 2 = AdamW.
+
+    ``clip_grad`` / ``lr_schedule``: the reference's clip_by_global_norm and warm-up-cosine schedule
+    (train.py:22-27,214-220).  ``lr_schedule=None`` keeps the constant ``lr * global_batch / 512``; a
+    ``WarmupCosine`` is taken as given (``reference_schedule`` builds the reference's).  The clip
+    sees the gradient the update consumes -- after the all-reduce in every collective mode: the
+    norm is part of the optimizer step, which every mode runs behind its join with the collectives.
+    With the one-launch FusedAdamW both live on the device (graph-replayable); with
+    ``torch.optim.AdamW`` (CPU or non-fp32 parameters) the same semantics run eagerly in torch ops
+    and ``graph=True`` is refused.  ``lr_now`` / ``grad_norm``: the last update's rate and norm."""
 
     def __init__(self, model: torch.nn.Module, global_batch: int, lr: float = 5e-4, weight_decay: float = 1e-4,
                  label_smoothing: float = 0.1, bucket_cap_mb: float = 25.0, device: Optional[torch.device] = None,
                  graph: bool = False, input_layout: str = "NHWC", flat_grads: Optional[bool] = None,
                  grad_sinks: bool = True, two_graphs: Optional[bool] = None, persistent_casts: bool = True,
-                 wgrad_stream: Optional[bool] = None):
+                 wgrad_stream: Optional[bool] = None, clip_grad: Optional[float] = None,
+                 lr_schedule: Optional[WarmupCosine] = None):
+        self.clip_grad = _check_clip(clip_grad)
+        if lr_schedule is not None and not isinstance(lr_schedule, WarmupCosine):
+            raise TypeError("TrainStep: lr_schedule must be a WarmupCosine or None")
+        self.lr_schedule = lr_schedule
         # input_layout "HWCN": the batch arrives as the reference's train-step feed [H, W, C, N]
         # (train.py:80, input_pipeline.py:187-191) and the model's patch GEMM gathers from it
         self.input_layout = input_layout
@@ -285,6 +398,12 @@ class TrainStep:
         # FusedAdamW
         on_gpu = all(p.is_cuda for p in params)
         self.flat = (self.pg or on_gpu) if flat_grads is None else bool(flat_grads)
+        # the one-launch FusedAdamW (fp32 GPU parameters in the flat buffer); torch.optim.AdamW otherwise
+        fused = self.flat and on_gpu and all(p.dtype == torch.float32 and p.is_contiguous() for p in params)
+        if self.graph and not fused and (self.clip_grad is not None or lr_schedule is not None):
+            raise ValueError("TrainStep: clip_grad / lr_schedule with graph=True need the one-launch FusedAdamW "
+                             "(fp32 contiguous GPU parameters, flat gradients); torch.optim.AdamW applies them "
+                             "eagerly from the host")
         if not self.pg:
             self.collective = "none"
         elif on_gpu and dist.get_backend() == "gloo":
@@ -342,6 +461,9 @@ class TrainStep:
             offs, n = flat_layout(params)
             self._offs = offs
             dev = params[0].device
+            # zeros: the alignment padding between the views is never written by anything (the
+            # kernels and autograd write the views, _zero_grad writes zeros, a SUM all-reduce of
+            # zeros is zero), so it stays zero and the global norm may run over the whole buffer
             self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
             for p, off in zip(params, offs):
                 p.grad = self._flat[off:off + p.numel()].view_as(p)
@@ -383,11 +505,15 @@ class TrainStep:
         base_lr = lr * (global_batch / 512)
         kw = dict(lr=base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay)
         self.opt = None
-        if self.flat and on_gpu and all(p.dtype == torch.float32 and p.is_contiguous() for p in params):
+        if fused:
             # the bf16 Dense copies written by the update (models that name them, bf16 compute)
             groups = model.cast_groups() if persistent_casts and hasattr(model, "cast_groups") else None
-            self.opt = FusedAdamW(params, self._flat, cast_groups=groups, **kw)
+            self.opt = FusedAdamW(params, self._flat, cast_groups=groups, clip_grad=self.clip_grad,
+                                  lr_schedule=lr_schedule, **kw)
         else:
+            # the torch optimizer: clip and schedule in torch ops before its step (_opt_step)
+            self._count = 0
+            self._lr_now = self._grad_norm = None
             if self.graph:
                 kw["capturable"] = True   # step counters on the device: replayable
             try:
@@ -605,10 +731,43 @@ class TrainStep:
                     ops.occupy_cus(self._comm, ch, usec, threads=thr, lds_bytes=lds)
         torch.cuda.current_stream(dev).wait_stream(self._comm)
 
+    def _opt_step(self):
+        """The optimizer step.  FusedAdamW clips and schedules on the device; for torch.optim.AdamW
+        the same chain in torch ops: the global norm of every gradient (fp64 sum of squares), optax's
+        clip factor multiplied into the gradients in place, the schedule's value at the number of
+        updates applied written to the parameter groups."""
+        if isinstance(self.opt, FusedAdamW) or (self.clip_grad is None and self.lr_schedule is None):
+            self.opt.step()
+            return
+        if self.clip_grad is not None:
+            grads = [p.grad for p in self._params if p.grad is not None]
+            norm = torch.stack([g.double().square().sum() for g in grads]).sum().sqrt().float()
+            scale = torch.where(norm < self.clip_grad, torch.ones_like(norm), self.clip_grad / norm)
+            torch._foreach_mul_(grads, scale)   # a NaN norm reaches every gradient: nothing is skipped
+            self._grad_norm = norm
+        if self.lr_schedule is not None:
+            self._lr_now = self.lr_schedule.value(self._count)
+            for group in self.opt.param_groups:
+                group["lr"] = self._lr_now
+        self._count += 1
+        self.opt.step()
+
+    @property
+    def lr_now(self):
+        """The rate of the last update: a 0-d device tensor (FusedAdamW, no sync) or a float; None
+        when neither clip_grad nor lr_schedule is set."""
+        return self.opt.lr_now if isinstance(self.opt, FusedAdamW) else self._lr_now
+
+    @property
+    def grad_norm(self):
+        """The global gradient norm (before clipping) of the last update, a 0-d tensor; None without
+        clip_grad."""
+        return self.opt.grad_norm if isinstance(self.opt, FusedAdamW) else self._grad_norm
+
     def _eager(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         loss = self._fwd_bwd(images, labels)
         self._allreduce()
-        self.opt.step()
+        self._opt_step()
         return loss
 
     def _capture(self, images: torch.Tensor, labels: torch.Tensor):
@@ -677,7 +836,7 @@ class TrainStep:
                 with torch.cuda.graph(g, capture_error_mode=mode):
                     self._loss = self._fwd_bwd(self._images, self._labels)
                 with torch.cuda.graph(go, capture_error_mode=mode):
-                    self.opt.step()
+                    self._opt_step()
                 self._g, self._g_opt = g, go
             ok = True
         except RuntimeError as e:   # an op that cannot be captured: stay eager, say so once

@@ -11,6 +11,7 @@
 //   * the attention route queries against their entry points, over a sweep of descriptors.
 // Launchers whose arguments pass validation would launch: with no GPU the HIP launch fails and
 // the ABI reports SAE_EHIP, which is the expected outcome here (no device memory is touched).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -209,6 +210,35 @@ static void validation() {
   expect(sae_smoothed_ce_fwd(nullptr, 0, 1000, q, 1000, SAE_DTYPE_BF16, static_cast<const int64_t*>(fake()), 0.1f,
                              fa, fa, fa) != SAE_OK,
          "ce zero rows");
+  // clip + schedule around AdamW: every refusal on the host, the schedule read from the caller's struct only
+  {
+    int32_t* step = static_cast<int32_t*>(fake());
+    float* hyper = static_cast<float*>(fake(16));
+    void* ws = fake(sae_adamw_prepare_workspace_bytes(100000));
+    sae_lr_schedule* s = new sae_lr_schedule{SAE_LR_WARMUP_COSINE, 0.f, 1e-3f, 1e-5f, 2, 10};
+    expect(sae_adamw_prepare(nullptr, 100000, fa, 1.f, nullptr, step, ws, hyper) == SAE_EINVAL, "prepare null schedule");
+    expect(sae_adamw_prepare(nullptr, 0, fa, 1.f, s, step, ws, hyper) == SAE_EINVAL, "prepare n 0 with buffers");
+    expect(sae_adamw_prepare(nullptr, 100000, fa, 0.f, s, step, ws, hyper) == SAE_EINVAL, "prepare max_norm 0");
+    expect(sae_adamw_prepare(nullptr, 100000, fa, NAN, s, step, ws, hyper) == SAE_EINVAL, "prepare max_norm NaN");
+    s->decay_steps = 2;
+    expect(sae_adamw_prepare(nullptr, 100000, fa, 1.f, s, step, ws, hyper) == SAE_EINVAL, "prepare decay <= warmup");
+    s->decay_steps = 10;
+    s->peak = 0.f;
+    expect(sae_adamw_prepare(nullptr, 100000, fa, 1.f, s, step, ws, hyper) == SAE_EINVAL, "prepare peak 0");
+    s->peak = 1e-3f;
+    int rc2 = sae_adamw_prepare(nullptr, 100000, fa, INFINITY, s, step, ws, hyper);
+    expect(rc2 == SAE_OK || rc2 == SAE_EHIP, "prepare: valid launch without a GPU");
+    rc2 = sae_adamw_prepare(nullptr, 0, nullptr, INFINITY, s, step, nullptr, hyper);
+    expect(rc2 == SAE_OK || rc2 == SAE_EHIP, "prepare, schedule alone: valid launch without a GPU");
+    expect(sae_adamw_step_dev(nullptr, 1, nullptr, 0, nullptr, step, hyper, 0.9f, 0.999f, 1e-8f, 1e-4f) == SAE_EINVAL,
+           "step_dev null chunks");
+    expect(sae_adamw_step_dev(nullptr, 0, nullptr, 0, nullptr, step, nullptr, 0.9f, 0.999f, 1e-8f, 1e-4f) == SAE_EINVAL,
+           "step_dev null hyper");
+    delete s;
+    for (int64_t n : {(int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)SAE_ADAMW_NORM_SPAN, (int64_t)1 << 40})
+      expect(sae_adamw_prepare_workspace_bytes(n) == (n < 1 ? 0 : (size_t)((n - 1) / SAE_ADAMW_NORM_SPAN + 1) * 8),
+             "prepare workspace bytes");
+  }
   expect(sae_abi_version() == SAE_ABI_VERSION, "abi version");
   expect(std::strlen(sae_build_info()) > 0, "build info");
 }
