@@ -151,11 +151,8 @@ class Encoder(nn.Module):
         if blocks and blocks[0].dtype == torch.bfloat16 and ops.layer_norm_ok(x):
             # cait.py:30-60 per block, every residual add fused with the LayerNorm that follows it
             # (this block's LayerNorm_1, the next block's LayerNorm_0): one HBM pass each
-            ops.cast_weights(encoder_weight_groups(blocks))   # every Dense kernel, one launch
-            try:
+            with ops.forward_casts(encoder_weight_groups(blocks)):   # every Dense kernel, one launch
                 return self._fused(x, blocks, is_training)
-            finally:
-                ops.clear_weight_cache()
         for blk in blocks:
             x = blk(x, is_training)
         return x

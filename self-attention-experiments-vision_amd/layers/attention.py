@@ -115,7 +115,7 @@ class AttentionBlock(nn.Module):
         self.DenseGeneral_0 = DenseGeneral((H, head_ch), (out_ch,), self.use_bias, device)
 
     def weight_groups(self):
-        """The fp32 kernels as the 2-D column blocks the projections use (``ops.cast_weights``)."""
+        """The fp32 kernels as the 2-D column blocks the projections use (``ops.forward_casts``)."""
         if self._in_ch is None:
             return []
         C, HD = self._in_ch, self.num_heads * self._head_ch_eff

@@ -18,6 +18,8 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
+import functools
 import math
 import os
 from typing import Optional, Tuple
@@ -26,7 +28,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "weight_cast", "cast_weights", "clear_weight_cache", "gemm_dw", "set_weight_grad_stream", "join_weight_grad_stream", "layer_norm", "add_layer_norm", "dropout_rows", "dropout_rows_mask", "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed", "relpos_bias", "rotary",
+__all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "weight_cast", "forward_casts", "clear_weight_cache", "gemm_dw", "layer_norm", "add_layer_norm", "dropout_rows", "dropout_rows_mask", "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed", "relpos_bias", "rotary",
            "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer"]
 
 
@@ -61,30 +63,48 @@ class KernelTimer:
 _TIMER = None
 
 
-def _sinking(bwd):
-    """Backward of an op that may write gradient sinks (the flat DP buffer, see set_grad_sinks):
-    once its kernels are enqueued, report every sink it claimed to the sink listener (the training
-    step launches a gradient bucket's all-reduce as soon as all of the bucket's gradients are
-    written, overlapping it with the rest of the backward)."""
-    import functools
+# The GradSinks (sinks.py) whose backward() window is open, or None: the only training-step state
+# held here.  Sinks, written set, listener and weight-gradient side stream belong to that object.
+_ACTIVE_SINKS = None
 
+
+def _sinking(bwd):
+    """Backward of an op that may write gradient sinks (sinks.GradSinks): once its kernels are enqueued,
+    the active GradSinks reports every sink it claimed to its listener (the training step launches a
+    bucket's all-reduce once all of its gradients are written, beside the rest of the backward)."""
     @functools.wraps(bwd)
     def wrapped(ctx, *grads):
-        n0 = len(_CLAIM_LOG)
+        sinks = _ACTIVE_SINKS
+        if sinks is None:
+            return bwd(ctx, *grads)
+        n0 = len(sinks.claimed)
         out = bwd(ctx, *grads)
-        if len(_CLAIM_LOG) > n0:
-            done = _CLAIM_LOG[n0:]
-            del _CLAIM_LOG[n0:]
-            if _SINK_LISTENER is not None:
-                if _WG_STREAM is not None:
-                    # a sink may have been written on the weight-gradient stream: the listener's
-                    # collective waits on that stream, which first picks up the main stream's work
-                    _WG_STREAM.wait_stream(torch.cuda.current_stream(_WG_STREAM.device))
-                with torch.cuda.stream(_WG_STREAM) if _WG_STREAM is not None else contextlib.nullcontext():
-                    for ptr in done:
-                        _SINK_LISTENER(ptr)
+        if len(sinks.claimed) > n0:
+            sinks.report(n0)
         return out
     return wrapped
+
+
+def _sink(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The sink of parameter ``t`` in the open window (GradSinks.lookup); None outside one."""
+    return None if _ACTIVE_SINKS is None else _ACTIVE_SINKS.lookup(t)
+
+
+def _claim(sink: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """Mark a sink as written by this backward (GradSinks.claim: at most once per window)."""
+    if sink is not None and _ACTIVE_SINKS is None:
+        raise RuntimeError("gradient sink claimed outside the GradSinks.backward() window its forward ran in")
+    return sink if sink is None else _ACTIVE_SINKS.claim(sink)
+
+
+def _unsunk(g, sink):
+    """The gradient autograd should see: None when it went into a sink."""
+    return None if sink is not None else g
+
+
+def _grad_out(sink: Optional[torch.Tensor], shape, device) -> torch.Tensor:
+    """Where a backward kernel writes an fp32 parameter gradient: the claimed sink, or a fresh buffer."""
+    return _claim(sink) if sink is not None else torch.empty(shape, dtype=torch.float32, device=device)
 
 
 def occupy_cus(stream, workgroups: int, usec: float, threads: int = 256, lds_bytes: int = 64 * 1024) -> None:
@@ -547,7 +567,8 @@ class _TalkingHeads(torch.autograd.Function):
         do = _grad_in(do)
         dq, dk, dv = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (q, k, v))
         s1, s2 = ctx.sinks
-        dth1, dth2 = _th_bwd(q, k, v, th1, th2, lse, do, dq, dk, dv, ctx.scale, ctx.rope, _claim(s1), _claim(s2))
+        dth1, dth2 = _th_bwd(q, k, v, th1, th2, lse, do, dq, dk, dv, ctx.scale, ctx.rope,
+                             _grad_out(s1, th1.shape, th1.device), _grad_out(s2, th2.shape, th2.device))
         return (dq, dk, dv, _unsunk(dth1.to(ctx.th_dtypes[0]), s1), _unsunk(dth2.to(ctx.th_dtypes[1]), s2), None,
                 None)
 
@@ -574,7 +595,8 @@ class _TalkingHeadsPacked(torch.autograd.Function):
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
         s1, s2 = ctx.sinks
         dth1, dth2 = _th_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], th1, th2, lse, do, dqkv[:, :, 0],
-                             dqkv[:, :, 1], dqkv[:, :, 2], ctx.scale, ctx.rope, _claim(s1), _claim(s2))
+                             dqkv[:, :, 1], dqkv[:, :, 2], ctx.scale, ctx.rope,
+                             _grad_out(s1, th1.shape, th1.device), _grad_out(s2, th2.shape, th2.device))
         return dqkv, _unsunk(dth1.to(ctx.th_dtypes[0]), s1), _unsunk(dth2.to(ctx.th_dtypes[1]), s2), None, None
 
 
@@ -708,117 +730,19 @@ def rotary(x: torch.Tensor, base: float = 10000.0) -> torch.Tensor:
     return _Rotary.apply(x, float(base))
 
 
-# ------------------------------------------------------------------ gradient sinks (flat DP buffer)
-# The multi-rank step keeps every parameter gradient in one flat fp32 buffer (train.py).  Left to
-# autograd, each parameter gradient would be computed into a fresh tensor and then ADDED into its
-# zeroed flat view (one extra elementwise kernel per parameter, ~150 per DeiT-S step).  A sink is
-# that flat view: the backward kernels of this module (weight / bias GEMMs, LayerNorm dgamma /
-# dbeta, patch embedding) write the gradient straight into it and hand autograd None for that
-# parameter.  A parameter may feed at most one such op per backward (each Dense / LayerNorm of the
-# models is applied once per step); a second write raises instead of silently overwriting.
-_GRAD_SINKS = {}      # id(param) -> (weakref(param), fp32 view shaped like the param)
-_SINK_WRITTEN = set()
-_SINK_WINDOW = False  # sinks are used only between begin_backward_sinks() and end_backward_sinks()
-_CLAIM_LOG = []       # data pointers of the sinks claimed by the backward function now running
-_SINK_LISTENER = None  # called with a sink's data pointer once the kernel writing it is enqueued
-
-
-def set_grad_sinks(params, views=None) -> None:
-    """Register ``views[i]`` (fp32, contiguous, shaped like ``params[i]``) as the gradient sink of
-    ``params[i]``; ``params=None`` clears every sink."""
-    import weakref
-    if params is None:
-        _GRAD_SINKS.clear()
-        return
-    for p, v in zip(params, views):
-        if v.dtype != torch.float32 or not v.is_contiguous() or v.shape != p.shape:
-            raise ValueError("set_grad_sinks: a sink must be an fp32 contiguous view shaped like its parameter")
-        _GRAD_SINKS[id(p)] = (weakref.ref(p), v)
-
-
-def begin_backward_sinks() -> None:
-    """Open the sink window for one backward (the training step's): every sink may be written once
-    again.  Outside the window the ops ignore the sinks and hand autograd ordinary gradients, so a
-    backward outside a training step (gradient accumulation, a manual check) keeps autograd's
-    accumulate semantics."""
-    global _SINK_WINDOW
-    _SINK_WRITTEN.clear()
-    del _CLAIM_LOG[:]
-    _SINK_WINDOW = True
-
-
-def end_backward_sinks() -> None:
-    """Close the sink window (the written set stays readable until the next begin)."""
-    global _SINK_WINDOW
-    _SINK_WINDOW = False
-
-
-def set_sink_listener(fn) -> None:
-    """``fn(data_ptr)`` is called for every sink once the kernel that writes it has been enqueued on
-    the current stream (None: no listener)."""
-    global _SINK_LISTENER
-    _SINK_LISTENER = fn
-
-
-def _sink(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """The sink of parameter ``t`` (or of the parameter ``t`` is a full reshape view of), viewed as
-    ``t``'s shape; None when it has none."""
-    if t is None or not t.requires_grad or not _GRAD_SINKS or not _SINK_WINDOW:
-        return None
-    base = t if t._base is None else t._base
-    e = _GRAD_SINKS.get(id(base))
-    if e is None or e[0]() is not base or t.numel() != base.numel():
-        return None
-    g = base.grad   # a sink is live only while it is still the parameter's .grad (not replaced / reset)
-    if g is None or g.data_ptr() != e[1].data_ptr():
-        return None
-    return e[1].view(t.shape)
-
-
-def _claim(sink: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """Mark a sink as written by this backward (at most once per step)."""
-    if sink is not None:
-        key = sink.data_ptr()
-        if key in _SINK_WRITTEN:
-            raise RuntimeError("gradient sink written twice in one backward: a parameter feeds two ops")
-        _SINK_WRITTEN.add(key)
-        _CLAIM_LOG.append(key)
-    return sink
-
-
 # ------------------------------------------------------------------------------ projections
-# Side stream of the weight-gradient GEMMs (set_weight_grad_stream): inside the training step's
-# sink window, a weight gradient that goes into a sink is off the backward's critical path, so its
-# GEMM runs on this stream beside the input-gradient chain (LayerNorm / attention backward and the
-# next dX GEMM) instead of between them; the step joins it before the optimizer.
-_WG_STREAM = None
-
-
-def set_weight_grad_stream(stream) -> None:
-    """Run the sink-bound weight-gradient GEMMs of the following backwards on ``stream`` (None:
-    on the current stream).  The caller joins it with :func:`join_weight_grad_stream`."""
-    global _WG_STREAM
-    _WG_STREAM = stream
-
-
-def join_weight_grad_stream() -> None:
-    """Make the current stream wait for every weight-gradient GEMM enqueued on the side stream."""
-    if _WG_STREAM is not None:
-        torch.cuda.current_stream(_WG_STREAM.device).wait_stream(_WG_STREAM)
-
-
 def gemm_dw(x2: torch.Tensor, dy2: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor] = None,
             accumulate: bool = False, jblock: int = 0, offload: bool = False) -> None:
     """dw (+)= x2^T dy2 and db (+)= colsum(dy2) in fp32 through ``sae_gemm_dw`` (split over the
     token axis, fixed-order reduction).  x2 [M, I], dy2 [M, J] bf16 with unit column stride.
     ``jblock`` > 0: dw is [J / jblock, I, jblock] (contiguous column blocks).  ``offload``: dw / db
     are gradient sinks nobody reads before the step's join, so the GEMM may run on the
-    weight-gradient side stream (when one is set and the sink window is open)."""
+    weight-gradient side stream of the open sink window (GradSinks.wgrad_stream; none outside one)."""
     lib = L.load()
     _require_gpu(x2, dy2, dw)
     M, I = x2.shape
     J = dy2.shape[1]
-    side = _WG_STREAM if (offload and _SINK_WINDOW and _WG_STREAM is not None) else None
+    side = _ACTIVE_SINKS.wgrad_stream if (offload and _ACTIVE_SINKS is not None) else None
     if side is not None:
         side.wait_stream(torch.cuda.current_stream(x2.device))   # x2 / dy2 are written on the main stream
         x2.record_stream(side)    # ... and stay allocated until the side stream has read them
@@ -891,129 +815,127 @@ def _dw_ok(x2: torch.Tensor, dy2: torch.Tensor) -> bool:
             and x2.data_ptr() % 16 == 0 and dy2.data_ptr() % 16 == 0)
 
 
-# ----------------------------------------------------- per-forward cache of the bf16 weight casts
-# ``cast_weights`` casts every Dense kernel of an encoder in ONE launch (sae_weight_cast_multi) at
-# the start of its forward; the projections look their casts up while that forward runs and the
-# encoder clears the cache when it returns (nothing outlives the forward: the next optimizer step
-# changes the fp32 weights).  Keys are the fp32 weights' data pointers, checked with versions.
-_WCACHE = {}
+# ------------------------------------------------------------ registry of the bf16 weight copies
+# A group is a list of fp32 2-D Dense kernels [K, n_j] of one K, stacked along columns; its bf16
+# [K, sum n_j] copy and the transpose are served from ONE registry, keyed by the weights' data
+# pointers and checked against their version counters.  A per-forward entry (owner None) is cast by
+# ``forward_casts`` at the start of an encoder's forward and taken out when it returns (the next
+# optimizer step changes the fp32 weights).  A persistent entry belongs to an optimizer that writes
+# the copies as it updates (FusedAdamW with cast_groups, sae_adamw_step_cast): the forward neither
+# casts nor allocates for it.  That update goes through raw pointers (no version bump); an in-place
+# change of a weight OUTSIDE it (load_state_dict, a copy_) bumps the version counter, and the next
+# lookup or ``refresh_persistent_casts`` re-casts into the same buffers.
+@dataclasses.dataclass
+class _CastEntry:
+    versions: tuple        # the weights' version counters when the copies were written
+    w16: torch.Tensor      # bf16 [K, N]
+    wt16: torch.Tensor     # bf16 [N, K]
+    weights: list          # the fp32 kernels (held: their addresses cannot be reused while registered)
+    owner: object = None   # who keeps the copies current; None: a per-forward entry
 
 
-def _wkey(ws):
+_CASTS = {}
+
+
+def _cast_key(ws):
     return tuple(w.data_ptr() for w in ws)
 
 
-def cast_weights(groups) -> None:
-    """``groups``: lists of fp32 2-D weights [K, n_j] (same K) stacked along columns; each group
-    gets a bf16 [K, sum n_j] and its transpose, cached under the group's key."""
-    lib = L.load()
+def _versions(ws):
+    return tuple(w._version for w in ws)
+
+
+def _run_casts(entries) -> None:
+    """Cast every entry's fp32 weights into its bf16 buffers, all in one launch."""
     items = []
-    dev = None
+    for e in entries:
+        K, N = e.w16.shape
+        col = 0
+        for w in e.weights:
+            items.append(L.WeightCastItem(w.data_ptr(), e.w16.data_ptr(), e.wt16.data_ptr(), K, w.shape[1], N, K, col))
+            col += w.shape[1]
+        e.versions = _versions(e.weights)
+    if items:
+        arr = (L.WeightCastItem * len(items))(*items)
+        L.check(L.load().sae_weight_cast_multi(_stream(entries[0].weights[0]), len(items), arr))
+
+
+@contextlib.contextmanager
+def forward_casts(groups):
+    """For the ``with`` body (one encoder forward), serve each of ``groups`` a bf16 copy cast here, in one
+    launch.  A group that is not 2-D fp32 contiguous with one K is skipped (its projections cast for
+    themselves), as is one an optimizer already serves.  On exit only the entries added here go."""
+    added = []
     for ws in groups:
         K = ws[0].shape[0]
         if any(w.dim() != 2 or w.shape[0] != K or w.dtype != torch.float32 or not w.is_contiguous() for w in ws):
             continue
-        if _wkey(ws) in _PERSIST:   # the optimizer keeps this group's copies
+        key = _cast_key(ws)
+        if key in _CASTS and _CASTS[key].owner is not None:   # the optimizer keeps this group's copies
             continue
-        dev = ws[0].device
         N = sum(w.shape[1] for w in ws)
-        w16 = torch.empty((K, N), dtype=torch.bfloat16, device=dev)
-        wt16 = torch.empty((N, K), dtype=torch.bfloat16, device=dev)
-        items += _cast_items(ws, w16, wt16)
-        _WCACHE[_wkey(ws)] = (tuple(w._version for w in ws), w16, wt16)
-    if items:
-        arr = (L.WeightCastItem * len(items))(*items)
-        L.check(lib.sae_weight_cast_multi(_stream(groups[0][0]), len(items), arr))
+        e = _CASTS[key] = _CastEntry((), torch.empty((K, N), dtype=torch.bfloat16, device=ws[0].device),
+                                     torch.empty((N, K), dtype=torch.bfloat16, device=ws[0].device), list(ws))
+        added.append((key, e))
+    try:
+        _run_casts([e for _, e in added])
+        yield
+    finally:
+        for key, e in added:
+            if _CASTS.get(key) is e:
+                del _CASTS[key]
 
 
 def clear_weight_cache() -> None:
-    _WCACHE.clear()
+    """Drop every per-forward entry now, an open ``forward_casts`` block's included (a reset for callers)."""
+    for key in [k for k, e in _CASTS.items() if e.owner is None]:
+        del _CASTS[key]
 
 
-# ---------------------------------------------------------- persistent bf16 weight copies
-# Groups whose bf16 copies the optimizer writes (FusedAdamW with cast_groups: the update and the
-# cast in one pass, sae_adamw_step_cast) stay registered across steps: the forward neither casts
-# nor allocates for them.  An in-place change of a weight OUTSIDE the optimizer (load_state_dict,
-# a copy_) bumps its version counter; the next lookup then re-casts into the same buffers.  The
-# optimizer writes through raw pointers (no version bump) and calls ``persistent_casts_fresh``
-# whenever it rewrites the copies itself.
-_PERSIST = {}
+def register_persistent_casts(groups, w16s, wt16s, owner) -> None:
+    """Serve ``groups``' bf16 copies from ``w16s`` / ``wt16s``, kept current from now on by ``owner``
+    (the optimizer that writes them; not None), and cast the weights' present values into them.
+    A later registration of the same weights takes over."""
+    if owner is None:
+        raise ValueError("register_persistent_casts: a persistent entry needs an owner")
+    entries = [_CastEntry((), w16, wt16, list(ws), owner) for ws, w16, wt16 in zip(groups, w16s, wt16s)]
+    _CASTS.update((_cast_key(e.weights), e) for e in entries)
+    _run_casts(entries)
 
 
-def register_persistent_casts(groups, w16s, wt16s, owner=None) -> None:
-    """Serve ``groups``' bf16 copies from ``w16s`` / ``wt16s`` (kept current by ``owner``, the
-    optimizer that writes them).  A later registration of the same weights takes over."""
-    for ws, w16, wt16 in zip(groups, w16s, wt16s):
-        _PERSIST[_wkey(ws)] = [tuple(w._version for w in ws), w16, wt16, list(ws), owner]
-
-
-def unregister_persistent_casts(groups, owner=None) -> None:
-    """Stop serving ``groups``' copies -- only the entries ``owner`` registered (None: any)."""
-    for ws in groups:
-        e = _PERSIST.get(_wkey(ws))
-        if e is not None and (owner is None or e[4] is owner):
-            del _PERSIST[_wkey(ws)]
+def unregister_persistent_casts(owner) -> None:
+    """Stop serving the copies ``owner`` registered (and still owns: not those taken over since)."""
+    for key in [k for k, e in _CASTS.items() if e.owner is owner]:
+        del _CASTS[key]
 
 
 def release_persistent_casts(params) -> None:
-    """Drop every registered group holding one of ``params`` (an optimizer that now updates them
+    """Drop every persistent group holding one of ``params`` (an optimizer that now updates them
     without writing those copies takes them over: the copies would go stale)."""
     ids = {p.data_ptr() for p in params}
-    for key in [k for k, e in _PERSIST.items() if any(w.data_ptr() in ids for w in e[3])]:
-        del _PERSIST[key]
+    for key in [k for k, e in _CASTS.items()
+                if e.owner is not None and any(w.data_ptr() in ids for w in e.weights)]:
+        del _CASTS[key]
 
 
-def persistent_casts_stale(groups) -> bool:
-    """True when a weight of a registered group was changed in place since its copies were
-    written (load_state_dict, copy_: the version counter moved)."""
-    for ws in groups:
-        e = _PERSIST.get(_wkey(ws))
-        if e is not None and e[0] != tuple(w._version for w in e[3]):
-            return True
-    return False
-
-
-def persistent_casts_fresh(groups) -> None:
-    """The copies of ``groups`` match their fp32 weights as of now."""
-    for ws in groups:
-        e = _PERSIST.get(_wkey(ws))
-        if e is not None:
-            e[0] = tuple(w._version for w in ws)
-
-
-def _cast_items(ws, w16, wt16):
-    K, N = ws[0].shape[0], w16.shape[1]
-    items, col = [], 0
-    for w in ws:
-        items.append(L.WeightCastItem(w.data_ptr(), w16.data_ptr(), wt16.data_ptr(), K, w.shape[1], N, K, col))
-        col += w.shape[1]
-    return items
-
-
-def recast_persistent(groups) -> None:
-    """Re-cast the registered copies of ``groups`` from their fp32 weights (one launch)."""
-    items = []
-    for ws in groups:
-        e = _PERSIST.get(_wkey(ws))
-        if e is not None:
-            items += _cast_items(e[3], e[1], e[2])
-            e[0] = tuple(w._version for w in e[3])
-    if items:
-        arr = (L.WeightCastItem * len(items))(*items)
-        L.check(L.load().sae_weight_cast_multi(_stream(groups[0][0]), len(items), arr))
+def refresh_persistent_casts(groups, only_if_stale: bool = False) -> None:
+    """Re-cast the persistent copies of ``groups`` from their fp32 weights (one launch); with
+    ``only_if_stale`` only when a weight of one was changed in place since (its version moved)."""
+    entries = [e for e in (_CASTS.get(_cast_key(ws)) for ws in groups) if e is not None and e.owner is not None]
+    if not only_if_stale or any(e.versions != _versions(e.weights) for e in entries):
+        _run_casts(entries)
 
 
 def _cast_lookup(ws):
-    key = _wkey(ws)
-    e = _PERSIST.get(key)
-    if e is not None:
-        if e[0] != tuple(w._version for w in ws):
-            recast_persistent([ws])
-        return e[1], e[2]
-    e = _WCACHE.get(key)
-    if e is not None and e[0] == tuple(w._version for w in ws):
-        return e[1], e[2]
-    return None
+    """(bf16 [K, N], bf16 [N, K]) of the group ``ws`` from the registry, or None."""
+    e = _CASTS.get(_cast_key(ws))
+    if e is None:
+        return None
+    if e.versions != _versions(e.weights):
+        if e.owner is None:   # a per-forward entry whose weight moved: stale, the caller casts
+            return None
+        _run_casts([e])
+    return e.w16, e.wt16
 
 
 def _cast(ws, dt):
@@ -1084,9 +1006,8 @@ class _Dense(torch.autograd.Function):
         sw, sb = ctx.sinks_w, ctx.sink_b
         if _dw_ok(x2, dy2) and (blocked or len(widths) == 1):
             # flat-buffer sinks (multi-rank step): dW / db written in place, autograd gets None
-            db = _claim(sb) if sb is not None else (
-                torch.empty((J,), dtype=torch.float32, device=x2.device) if ctx.has_b else None)
-            rdb = None if sb is not None else db
+            db = _grad_out(sb, (J,), x2.device) if ctx.has_b else None
+            rdb = _unsunk(db, sb)
             if blocked:   # one contiguous [I, n] gradient per column block: no slice copies
                 n = widths[0]
                 s0 = sw[0]
@@ -1126,18 +1047,17 @@ class _Dense(torch.autograd.Function):
         I, J = wd.shape
         dx = gemm_f32(dy2, wd.t()).view(ctx.xshape).to(ctx.xdtype)
         sb = ctx.sink_b
-        db = _claim(sb) if sb is not None else (
-            torch.empty((J,), dtype=torch.float32, device=x2.device) if ctx.has_b else None)
+        db = _grad_out(sb, (J,), x2.device) if ctx.has_b else None
         dws, col = [], 0
         for (n, wdt), sw in zip(ctx.wmeta, ctx.sinks_w):
-            dst = _claim(sw) if sw is not None else torch.empty((I, n), dtype=torch.float32, device=x2.device)
+            dst = _grad_out(sw, (I, n), x2.device)
             dyb = dy2[:, col:col + n]
             if not _f32_operand_ok(dyb):
                 dyb = dyb.contiguous()
             gemm_f32(x2.t(), dyb, out=dst, colsum=db[col:col + n] if db is not None else None)
             dws.append(None if sw is not None else dst.to(wdt))
             col += n
-        return (dx, None if sb is not None else db, None, *dws)
+        return (dx, _unsunk(db, sb), None, *dws)
 
 
 def dense(x: torch.Tensor, w, b: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
@@ -1210,9 +1130,8 @@ class _PatchEmbed(torch.autograd.Function):
         desc = ctx.desc
         dout = dout.to(torch.bfloat16).contiguous()
         sw, sb = ctx.sinks   # flat-buffer sinks (multi-rank step): written in place
-        dw = _claim(sw) if sw is not None else torch.empty(ctx.wshape, dtype=torch.float32, device=dout.device)
-        db = _claim(sb) if sb is not None else (
-            torch.empty((ctx.wshape[1],), dtype=torch.float32, device=dout.device) if ctx.has_b else None)
+        dw = _grad_out(sw, ctx.wshape, dout.device)
+        db = _grad_out(sb, (ctx.wshape[1],), dout.device) if ctx.has_b else None
         if ctx.gathered:   # dW = P^T dY, db = colsum(dY) on the weight-gradient kernel
             gemm_dw(saved, dout.view(-1, ctx.wshape[1]), dw, db)
         else:
@@ -1372,16 +1291,14 @@ class _FFBlock(torch.autograd.Function):
         dh = gemm_nt(dy2, w1p, None, EPI_MUL_AUX if ctx.gg else EPI_DGELU, aux=h)   # dA W1^T, times gelu'(h)
         sw0, sb0, sw1, sb1 = ctx.sinks   # flat-buffer sinks (multi-rank step): written in place
         dev = dy2.device
-        dw1 = _claim(sw1) if sw1 is not None else torch.empty((Hd, O), dtype=torch.float32, device=dev)
-        db1 = _claim(sb1) if sb1 is not None else (
-            torch.empty((O,), dtype=torch.float32, device=dev) if ctx.has_b[1] else None)
+        dw1 = _grad_out(sw1, (Hd, O), dev)
+        db1 = _grad_out(sb1, (O,), dev) if ctx.has_b[1] else None
         gemm_dw(a, dy2, dw1, db1, offload=sw1 is not None and (sb1 is not None or not ctx.has_b[1]))
         dx = gemm_nt(dh, w0p)                                     # dH W0^T
-        dw0 = _claim(sw0) if sw0 is not None else torch.empty((I, Hd), dtype=torch.float32, device=dev)
-        db0 = _claim(sb0) if sb0 is not None else (
-            torch.empty((Hd,), dtype=torch.float32, device=dev) if ctx.has_b[0] else None)
+        dw0 = _grad_out(sw0, (I, Hd), dev)
+        db0 = _grad_out(sb0, (Hd,), dev) if ctx.has_b[0] else None
         gemm_dw(x2, dh, dw0, db0, offload=sw0 is not None and (sb0 is not None or not ctx.has_b[0]))
-        ret = [None if sk is not None else g for sk, g in zip(ctx.sinks, (dw0, db0, dw1, db1))]
+        ret = [_unsunk(g, sk) for sk, g in zip(ctx.sinks, (dw0, db0, dw1, db1))]
         return (dx.view(ctx.xshape).to(ctx.xdtype), *ret, None)
 
 
@@ -1459,8 +1376,8 @@ def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None), dr
     dy = _bf16c(dy)
     dx = torch.empty_like(xs)
     ddelta = torch.empty(xs.shape, dtype=torch.bfloat16, device=xs.device) if want_ddelta else None
-    dg = _claim(sinks[0]) if sinks[0] is not None else torch.empty(C, dtype=torch.float32, device=xs.device)
-    db = _claim(sinks[1]) if sinks[1] is not None else torch.empty(C, dtype=torch.float32, device=xs.device)
+    dg = _grad_out(sinks[0], (C,), xs.device)
+    db = _grad_out(sinks[1], (C,), xs.device)
     ws = torch.empty(lib.sae_layernorm_bwd_workspace_bytes(M, C), dtype=torch.uint8, device=xs.device)
     if dxin is not None:
         dxin = _f32c(dxin, "dxin")
@@ -1472,11 +1389,6 @@ def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None), dr
     L.check(lib.sae_layernorm_bwd(_stream(xs), M, C, _ptr(xs), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dy),
                                   _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db), _ptr(ws)))
     return dx, ddelta, dg, db
-
-
-def _unsunk(g, sink):
-    """The gradient autograd should see: None when it went into a sink."""
-    return None if sink is not None else g
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -1555,9 +1467,9 @@ class _AddLayerNormScaled(torch.autograd.Function):
         dx = torch.empty_like(xout)
         ddelta = torch.empty(xout.shape, dtype=torch.bfloat16, device=xout.device)
         sg, sbt, sls = ctx.sinks
-        dg = _claim(sg) if sg is not None else torch.empty(C, dtype=torch.float32, device=xout.device)
-        db = _claim(sbt) if sbt is not None else torch.empty(C, dtype=torch.float32, device=xout.device)
-        dls = _claim(sls) if sls is not None else torch.empty(C, dtype=torch.float32, device=xout.device)
+        dg = _grad_out(sg, (C,), xout.device)
+        db = _grad_out(sbt, (C,), xout.device)
+        dls = _grad_out(sls, (C,), xout.device)
         ws = torch.empty(lib.sae_layernorm_bwd_workspace_bytes(M, C), dtype=torch.uint8, device=xout.device)
         L.check(lib.sae_layernorm_bwd_scaled(_stream(xout), M, C, _ptr(xout), _ptr(mean), _ptr(rstd), _ptr(gamma),
                                              _ptr(dy), _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db),
@@ -1664,8 +1576,8 @@ class _EncoderTokens(torch.autograd.Function):
         dx = _f32c(dx, "dx")
         dtok = torch.empty((B, Lt, E), dtype=torch.bfloat16, device=dx.device)
         scls, spos = ctx.sinks
-        dcls = _claim(scls) if scls is not None else torch.empty(ctx.meta[0], dtype=torch.float32, device=dx.device)
-        dpos = _claim(spos) if spos is not None else torch.empty(ctx.meta[1], dtype=torch.float32, device=dx.device)
+        dcls = _grad_out(scls, ctx.meta[0], dx.device)
+        dpos = _grad_out(spos, ctx.meta[1], dx.device)
         if ctx.drop is not None:
             L.check(lib.sae_tokens_bwd_dropout(_stream(dx), B, Lt, E, _ptr(dx), _ptr(dtok), _ptr(dcls), _ptr(dpos),
                                                ctx.drop[0], _ptr(ctx.drop[1]), ctx.drop[2]))

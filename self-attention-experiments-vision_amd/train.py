@@ -4,7 +4,7 @@ One process per GPU, ``torch.distributed`` with backend ``nccl`` (= RCCL on ROCm
 xGMI.  The reference's ``jax.pmap(train_step)`` + ``lax.pmean(grads)`` (train.py:94-96,230)
 becomes: every parameter's gradient is a 16-byte-aligned view into ONE flat fp32 buffer, cut
 into buckets along parameter boundaries in the order the backward finishes them; the backward
-kernels write the gradients straight into their views (gradient sinks, ops.set_grad_sinks), and
+kernels write the gradients straight into their views (gradient sinks, sinks.GradSinks), and
 as soon as the last gradient of a bucket is written its SUM all-reduce (of the gradients of
 loss / world = the global-batch mean) is launched on a communication stream, overlapping the
 rest of the backward; the compute stream joins that stream before the one-launch AdamW.  On the
@@ -31,14 +31,21 @@ a clip norm put the learning rate and the clip factor into device memory, comput
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import math
 import os
+import weakref
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
+
+from . import _lib as L
+from . import ops
+from .sinks import GradSinks
 
 __all__ = ["smoothed_cross_entropy", "TrainStep", "init_distributed", "FusedAdamW", "WarmupCosine",
            "reference_schedule"]
@@ -91,7 +98,6 @@ def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, smoothing
     HIP loss (ops.smoothed_cross_entropy); CPU tensors (the multi-process gloo tests' small
     models) take torch's cross entropy, which computes the same quantity."""
     if logits.is_cuda:
-        from . import ops
         return ops.smoothed_cross_entropy(logits, labels, smoothing)
     return F.cross_entropy(logits.float(), labels, label_smoothing=smoothing)
 
@@ -162,6 +168,15 @@ def flat_layout(params, align: int = 4):
     return offs, off
 
 
+class _Slot(NamedTuple):
+    """One parameter of FusedAdamW: its index and the addresses of its gradient view and moments."""
+    index: int
+    param: torch.Tensor
+    grad: int
+    m: int
+    v: int
+
+
 class FusedAdamW:
     """AdamW (optax.adamw of train.py:25-27,229-233, torch.optim.AdamW's update order) for fp32 GPU
     parameters whose gradients live in one flat buffer: every parameter in one HIP launch
@@ -169,7 +184,7 @@ class FusedAdamW:
     two more flat buffers laid out like the gradients; the step counter stays on the device, so the
     update can be captured in a HIP graph and replayed.
 
-    ``cast_groups``: column-stacked groups of 2-D fp32 Dense kernels (the ``ops.cast_weights``
+    ``cast_groups``: column-stacked groups of 2-D fp32 Dense kernels (the ``ops.forward_casts``
     groups; each kernel a whole parameter, possibly reshaped) whose bf16 compute copies the
     update writes as it goes (``sae_adamw_step_cast``): the forward then reads persistent copies
     (``ops.register_persistent_casts``) instead of casting every weight at its start.  Parameter
@@ -186,9 +201,6 @@ class FusedAdamW:
     def __init__(self, params, flat_grad: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, cast_groups=None, clip_grad: Optional[float] = None,
                  lr_schedule: Optional[WarmupCosine] = None, monitor_norm: bool = False):
-        import ctypes
-        from . import _lib as L
-        from . import ops
         self.lib = L.load()
         self.params = list(params)
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
@@ -225,23 +237,23 @@ class FusedAdamW:
                     or not g.is_contiguous() or g.data_ptr() < flat_grad.data_ptr()):
                 raise ValueError("FusedAdamW: fp32 contiguous parameters with views of the flat gradient buffer")
             off = (g.data_ptr() - flat_grad.data_ptr()) // 4
-            slot[p.data_ptr()] = (i, p, g.data_ptr(), self.m.data_ptr() + 4 * off, self.v.data_ptr() + 4 * off)
+            slot[p.data_ptr()] = _Slot(i, p, g.data_ptr(), self.m.data_ptr() + 4 * off, self.v.data_ptr() + 4 * off)
         # the Dense kernels whose copies the update writes: whole parameters, shapes / alignment
         # the tile path takes (K, N, column offsets multiples of 4)
         self.cast_groups, self.copies = [], []
-        tiles_in = []
+        tiles_in = []   # per kernel: (slot, K, n, w16, wt16, N of its group, its first column)
         claimed = set()
         for ws in (cast_groups or []):
             K = ws[0].shape[0]
             ent = [slot.get(w.data_ptr()) for w in ws]
-            if (any(e is None or e[1].numel() != w.numel() for e, w in zip(ent, ws))
-                    or any(e[0] in claimed for e in ent)          # a parameter is updated once
-                    or len({e[0] for e in ent}) != len(ent)
+            if (any(e is None or e.param.numel() != w.numel() for e, w in zip(ent, ws))
+                    or any(e.index in claimed for e in ent)          # a parameter is updated once
+                    or len({e.index for e in ent}) != len(ent)
                     or any(w.dim() != 2 or w.shape[0] != K for w in ws)
                     or K % 4 or any(w.shape[1] % 4 for w in ws)
-                    or any(e[2] % 16 or e[3] % 16 or e[4] % 16 or e[1].data_ptr() % 16 for e in ent)):
+                    or any(e.grad % 16 or e.m % 16 or e.v % 16 or e.param.data_ptr() % 16 for e in ent)):
                 continue
-            claimed.update(e[0] for e in ent)
+            claimed.update(e.index for e in ent)
             N = sum(w.shape[1] for w in ws)
             w16 = torch.empty((K, N), dtype=torch.bfloat16, device=dev)
             wt16 = torch.empty((N, K), dtype=torch.bfloat16, device=dev)
@@ -251,48 +263,51 @@ class FusedAdamW:
                 col += w.shape[1]
             self.cast_groups.append(list(ws))
             self.copies.append((w16, wt16))
-        in_tiles = {e[0] for e, *_ in tiles_in}
-        flat_idx = [i for i in range(len(self.params)) if i not in in_tiles]
-        n = len(flat_idx)
-        P = (ctypes.c_void_p * max(1, n))()
-        G, M, V = (ctypes.c_void_p * max(1, n))(), (ctypes.c_void_p * max(1, n))(), (ctypes.c_void_p * max(1, n))()
-        Nn = (ctypes.c_int64 * max(1, n))()
-        for j, i in enumerate(flat_idx):
-            p = self.params[i]
-            _, _, G[j], M[j], V[j] = slot[p.data_ptr()]
-            P[j], Nn[j] = p.data_ptr(), p.numel()
-        cap = sum((self.params[i].numel() + L.SAE_ADAMW_CHUNK - 1) // L.SAE_ADAMW_CHUNK for i in flat_idx)
+        self._plan_chunks([p for i, p in enumerate(self.params) if i not in claimed], slot, dev)
+        self.n_tiles, self.tiles = 0, None
+        if tiles_in:
+            self._plan_cast_tiles(tiles_in, dev)
+            # the owner token: unregistering (close, finalizer) removes only this optimizer's
+            # entries; registering casts the initial weights into the copies
+            self._owner = object()
+            ops.register_persistent_casts(self.cast_groups, [c[0] for c in self.copies], [c[1] for c in self.copies],
+                                          self._owner)
+            # the registry holds the weights (their addresses cannot be reused while registered);
+            # it lets go of them with the optimizer
+            weakref.finalize(self, ops.unregister_persistent_casts, self._owner)
+
+    def _plan_chunks(self, params, slot, dev):
+        """The device chunk table of ``params``, which the flat path updates (``sae_adamw_plan``), built once."""
+        n = len(params)
+        arr = lambda t: (t * max(1, n))()
+        P, G, M, V = (arr(ctypes.c_void_p) for _ in range(4))
+        Nn = arr(ctypes.c_int64)
+        for j, p in enumerate(params):
+            s = slot[p.data_ptr()]
+            P[j], G[j], M[j], V[j], Nn[j] = p.data_ptr(), s.grad, s.m, s.v, p.numel()
+        cap = sum(-(-p.numel() // L.SAE_ADAMW_CHUNK) for p in params)
         table = (L.AdamwChunk * max(1, cap))()
         cnt = ctypes.c_int64(0)
         L.check(self.lib.sae_adamw_plan(n, P, G, M, V, Nn, table, cap, ctypes.byref(cnt)))
         self.n_chunks = int(cnt.value)
-        self.table = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(dev)   # device copy, built once
-        self.n_tiles = 0
-        self.tiles = None
-        if tiles_in:
-            k = len(tiles_in)
-            arr = lambda t: (t * k)()
-            P, G, M, V, W16, WT = (arr(ctypes.c_void_p) for _ in range(6))
-            Kx, Nx, LD, LT, C0 = (arr(ctypes.c_int32) for _ in range(5))
-            for j, (e, K, Nw, w16, wt16, Ntot, col) in enumerate(tiles_in):
-                P[j], G[j], M[j], V[j] = e[1].data_ptr(), e[2], e[3], e[4]
-                W16[j], WT[j] = w16.data_ptr(), wt16.data_ptr()
-                Kx[j], Nx[j], LD[j], LT[j], C0[j] = K, Nw, Ntot, K, col
-            cap = sum(-(-K // 64) * -(-Nw // 64) for _, K, Nw, *_ in tiles_in)
-            ttab = (L.AdamwCastTile * cap)()
-            L.check(self.lib.sae_adamw_cast_plan(k, P, G, M, V, Kx, Nx, W16, LD, WT, LT, C0, ttab, cap,
-                                                 ctypes.byref(cnt)))
-            self.n_tiles = int(cnt.value)
-            self.tiles = torch.frombuffer(bytearray(ttab), dtype=torch.uint8).to(dev)
-            # the owner token: unregistering (close, finalizer) removes only this optimizer's entries
-            self._owner = object()
-            ops.register_persistent_casts(self.cast_groups, [c[0] for c in self.copies], [c[1] for c in self.copies],
-                                          self._owner)
-            ops.recast_persistent(self.cast_groups)   # the copies of the initial weights
-            # the registry holds the weights (their addresses cannot be reused while registered);
-            # it lets go of them with the optimizer
-            import weakref
-            weakref.finalize(self, ops.unregister_persistent_casts, list(self.cast_groups), self._owner)
+        self.table = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(dev)
+
+    def _plan_cast_tiles(self, tiles_in, dev):
+        """The device 64 x 64 tile table of the kernels whose bf16 copies the update writes, built once."""
+        k = len(tiles_in)
+        arr = lambda t: (t * k)()
+        P, G, M, V, W16, WT = (arr(ctypes.c_void_p) for _ in range(6))
+        Kx, Nx, LD, LT, C0 = (arr(ctypes.c_int32) for _ in range(5))
+        for j, (e, K, Nw, w16, wt16, Ntot, col) in enumerate(tiles_in):
+            P[j], G[j], M[j], V[j] = e.param.data_ptr(), e.grad, e.m, e.v
+            W16[j], WT[j] = w16.data_ptr(), wt16.data_ptr()
+            Kx[j], Nx[j], LD[j], LT[j], C0[j] = K, Nw, Ntot, K, col
+        cap = sum(-(-K // 64) * -(-Nw // 64) for _, K, Nw, *_ in tiles_in)
+        ttab = (L.AdamwCastTile * cap)()
+        cnt = ctypes.c_int64(0)
+        L.check(self.lib.sae_adamw_cast_plan(k, P, G, M, V, Kx, Nx, W16, LD, WT, LT, C0, ttab, cap, ctypes.byref(cnt)))
+        self.n_tiles = int(cnt.value)
+        self.tiles = torch.frombuffer(bytearray(ttab), dtype=torch.uint8).to(dev)
 
     @property
     def lr_now(self):
@@ -306,8 +321,6 @@ class FusedAdamW:
         return None if self.hyper is None else self.hyper[2]
 
     def step(self):
-        import ctypes
-        from . import _lib as L
         b1, b2 = self.betas
         st = torch.cuda.current_stream(self.m.device).cuda_stream
         if self.hyper is not None:
@@ -328,26 +341,17 @@ class FusedAdamW:
             L.check(self.lib.sae_adamw_step(st, self.n_chunks, self.table.data_ptr(), self.step_count.data_ptr(),
                                             self.lr, b1, b2, self.eps, self.weight_decay))
 
-    def refresh_casts(self):
-        """Re-cast the copies after the parameters were overwritten outside the update."""
+    def refresh_casts(self, only_if_stale: bool = False):
+        """Re-cast the copies after the parameters were overwritten outside the update; with
+        ``only_if_stale`` only if a weight's version moved since (a replayed step graph holds no cast:
+        a load_state_dict after the capture would otherwise reach the forward one update late)."""
         if self.cast_groups:
-            from . import ops
-            ops.recast_persistent(self.cast_groups)
-
-    def refresh_if_stale(self):
-        """Re-cast the copies if a weight was changed in place since they were written: a replayed
-        step graph does not contain the cast, so a load_state_dict / copy_ after the capture would
-        otherwise reach the forward only after the next update.  Host-side version check."""
-        if self.cast_groups:
-            from . import ops
-            if ops.persistent_casts_stale(self.cast_groups):
-                ops.recast_persistent(self.cast_groups)
+            ops.refresh_persistent_casts(self.cast_groups, only_if_stale)
 
     def close(self):
         """Stop serving the copies (the forward casts per call again)."""
         if self.cast_groups:
-            from . import ops
-            ops.unregister_persistent_casts(self.cast_groups, self._owner)
+            ops.unregister_persistent_casts(self._owner)
             self.cast_groups = []
 
     def state_tensors(self):
@@ -388,6 +392,8 @@ class TrainStep:
         self.world = dist.get_world_size() if self.pg else 1
         self.graph = bool(graph) and torch.cuda.is_available()
         self._g = self._g_opt = None
+        # the flat ranges _zero_grad clears (None: the whole buffer); _note_sunk narrows them
+        self._zero_ranges = None
         self.model = model
         params = [p for p in model.parameters() if p.requires_grad]
         self._params = params
@@ -481,12 +487,6 @@ class TrainStep:
                 self._buckets.append((0, hi))
                 self._bucket_params.append(members)
             self._bucket_of = {i: b for b, ms in enumerate(self._bucket_params) for i in ms}
-            # the backward kernels write each parameter's gradient straight into its flat view
-            # (ops.set_grad_sinks) instead of autograd adding a fresh gradient tensor into it
-            self._sinks = bool(grad_sinks)
-            if self._sinks:
-                from . import ops
-                ops.set_grad_sinks(params, [p.grad for p in params])
             if self.collective == "overlap":
                 self._arm_overlap_hooks()
             if self._flagged:
@@ -495,13 +495,19 @@ class TrainStep:
                 self._flag_order = []   # bucket order of the captured bumps (the host's issue order)
                 self._epoch = 0
         # the sink-bound weight-gradient GEMMs run on a side stream beside the input-gradient chain
-        # (ops.set_weight_grad_stream), opt-in: SAE_WG_STREAM=1 or wgrad_stream=True.  Off by default: the
+        # (GradSinks.wgrad_stream), opt-in: SAE_WG_STREAM=1 or wgrad_stream=True.  Off by default: the
         # concurrent dW kernels push the persistent gemm8 tiles into a tail (DeiT-S 15,381 vs
         # 15,619 img/s, profiles/r05i_wgstream_rejected.txt)
         if wgrad_stream is None:
             wgrad_stream = os.environ.get("SAE_WG_STREAM", "0") == "1"
         self._wg = (torch.cuda.Stream(device=params[0].device)
-                    if wgrad_stream and self.flat and self._sinks and on_gpu else None)
+                    if wgrad_stream and self.flat and grad_sinks and on_gpu else None)
+        # the backward kernels write each parameter's gradient straight into its flat view (this step's
+        # GradSinks, live inside _fwd_bwd's window) instead of autograd adding a fresh tensor into it
+        self._sinks = None
+        if self.flat and grad_sinks:
+            self._sinks = GradSinks(params, [p.grad for p in params], wgrad_stream=self._wg,
+                                    listener=self._on_sink if self.collective == "overlap" else None)
         base_lr = lr * (global_batch / 512)
         kw = dict(lr=base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay)
         self.opt = None
@@ -528,7 +534,6 @@ class TrainStep:
         self._drop_rng = None
         if on_gpu and any(getattr(m, "attn_dropout_rate", 0.0) > 0.0 or getattr(m, "dropout_rate", 0.0) > 0.0
                           for m in model.modules()):
-            from . import ops
             self._drop_rng = ops.dropout_rng(params[0].device)
 
     @staticmethod
@@ -556,13 +561,11 @@ class TrainStep:
     # ---- the overlapped bucket all-reduce
     def _arm_overlap_hooks(self):
         """A parameter's gradient is final when the kernel writing its sink has been enqueued
-        (ops.set_sink_listener) or, for gradients autograd accumulates, after its accumulation
+        (_on_sink, the listener of this step's GradSinks) or, for gradients autograd accumulates, after its accumulation
         (post-accumulate-grad hook); the bucket holding it is launched once all of its parameters
         are final."""
-        from . import ops
         self._armed = False
         self._ptr_to_idx = {p.grad.data_ptr(): i for i, p in enumerate(self._params)}
-        ops.set_sink_listener(self._on_sink)
         for i, p in enumerate(self._params):
             p.register_post_accumulate_grad_hook(lambda _p, i=i: self._on_ready(i))
         if self._flat.is_cuda:
@@ -590,7 +593,6 @@ class TrainStep:
             return
         if self._flagged and torch.cuda.is_current_stream_capturing():
             # flagged graph: a mark on the captured chain; the collective is issued after the replay
-            from . import ops
             ops.flag_bump(self._flags, b)
             self._flag_order.append(b)
             return
@@ -599,15 +601,19 @@ class TrainStep:
             # bucket's gradient kernels included) and runs the RCCL all-reduce beside the rest of
             # the backward; inside a graph capture this is a fork of the captured graph
             self._comm.wait_stream(torch.cuda.current_stream(t.device))
-            with torch.cuda.stream(self._comm):
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self._cpg)
-                if self._emulate is not None:
-                    from . import ops
-                    ch, bw, wd, lds, thr = self._emulate
-                    usec = 2.0 * (wd - 1) / wd * t.numel() * 4 / (bw * 1e3)
-                    ops.occupy_cus(self._comm, ch, usec, threads=thr, lds_bytes=lds)
+            self._allreduce_on_comm(t)
         else:
             self._works.append(dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=True))
+
+    def _allreduce_on_comm(self, t):
+        """The SUM all-reduce of bucket ``t`` on the communication stream, which the caller has made
+        wait for the bucket's gradients; under the RCCL emulation, the occupancy kernel behind it."""
+        with torch.cuda.stream(self._comm):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self._cpg)
+            if self._emulate is not None:
+                ch, bw, wd, lds, thr = self._emulate
+                usec = 2.0 * (wd - 1) / wd * t.numel() * 4 / (bw * 1e3)
+                ops.occupy_cus(self._comm, ch, usec, threads=thr, lds_bytes=lds)
 
     def _begin_overlap(self):
         self._ready = set()
@@ -632,11 +638,10 @@ class TrainStep:
     # ---- pieces of one step
     def _zero_grad(self):
         if self.flat:
-            ranges = getattr(self, "_zero_ranges", None)
-            if ranges is None:
+            if self._zero_ranges is None:
                 self._flat.zero_()
             else:   # only the gradients autograd accumulates (every sink is overwritten)
-                for lo, hi in ranges:
+                for lo, hi in self._zero_ranges:
                     self._flat[lo:hi].zero_()
         else:
             self.opt.zero_grad(set_to_none=True)
@@ -645,12 +650,10 @@ class TrainStep:
         """After a graph-mode backward: the flat ranges of the parameters whose gradients did NOT
         go through a sink (autograd adds into those, so they need zeroing before the next
         backward).  Graph mode only: the captured step writes the same sinks on every replay."""
-        from . import ops
-        written = set(ops._SINK_WRITTEN)
         ranges = []
         for p, off in zip(self._params, self._offs):
             n = p.numel()
-            if p.grad is None or p.grad.data_ptr() not in written:
+            if p.grad is None or p.grad.data_ptr() not in self._sinks.written:
                 if ranges and ranges[-1][1] == off:
                     ranges[-1] = (ranges[-1][0], off + n)
                 else:
@@ -659,37 +662,31 @@ class TrainStep:
         self._zero_ranges = ranges if len(ranges) <= 8 else None
 
     def _fwd_bwd(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        from . import ops
         if self._drop_rng is not None:
             self._drop_rng.advance()
         self._zero_grad()
-        sinks = self.flat and self._sinks
+        sinks = self._sinks
         overlap = self.collective == "overlap"
-        if sinks:
-            ops.begin_backward_sinks()   # the sink window: this step's forward + backward only
-            ops.set_weight_grad_stream(self._wg)
-        try:
-            if overlap:
-                self._begin_overlap()
-            if self.input_layout == "NHWC":
-                logits = self.model(images, is_training=True)
-            else:
-                logits = self.model(images, is_training=True, layout=self.input_layout)
-            loss = smoothed_cross_entropy(logits, labels, self.smoothing)
-            # world > 1: the SUM all-reduce of the per-rank gradients of loss / world is the
-            # gradient of the global-batch mean (survey D9)
-            (loss / self.world if self.world > 1 else loss).backward()
-            if sinks:
-                ops.join_weight_grad_stream()   # every weight gradient written before the update
-            if overlap:
-                self._end_overlap()
+        try:   # (the sink window: this step's forward + backward only)
+            with sinks.backward() if sinks is not None else contextlib.nullcontext():
+                if overlap:
+                    self._begin_overlap()
+                if self.input_layout == "NHWC":
+                    logits = self.model(images, is_training=True)
+                else:
+                    logits = self.model(images, is_training=True, layout=self.input_layout)
+                loss = smoothed_cross_entropy(logits, labels, self.smoothing)
+                # world > 1: the SUM all-reduce of the per-rank gradients of loss / world is the
+                # gradient of the global-batch mean (survey D9)
+                (loss / self.world if self.world > 1 else loss).backward()
+                if sinks is not None:
+                    sinks.join()   # every weight gradient written before the update
+                if overlap:
+                    self._end_overlap()
         finally:
-            if sinks:
-                ops.end_backward_sinks()
-                ops.set_weight_grad_stream(None)
             if overlap:
                 self._armed = False
-        if sinks and self.graph and not torch.cuda.is_current_stream_capturing():
+        if sinks is not None and self.graph and not torch.cuda.is_current_stream_capturing():
             self._note_sunk()
         return loss.detach()
 
@@ -716,20 +713,12 @@ class TrainStep:
         """After a replay of the flagged forward + backward graph: on the communication stream, each
         bucket's wait for its flag (bumped by this replay) and its all-reduce, in the captured order;
         the compute stream joins the communication stream before the optimizer's graph."""
-        from . import ops
         self._epoch += 1
-        dev = self._flat.device
         for b in self._flag_order:
             lo, hi = self._buckets[b]
-            t = self._flat[lo:hi]
             ops.stream_wait_flag(self._comm, self._flags, b, self._epoch)
-            with torch.cuda.stream(self._comm):
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self._cpg)
-                if self._emulate is not None:
-                    ch, bw, wd, lds, thr = self._emulate
-                    usec = 2.0 * (wd - 1) / wd * t.numel() * 4 / (bw * 1e3)
-                    ops.occupy_cus(self._comm, ch, usec, threads=thr, lds_bytes=lds)
-        torch.cuda.current_stream(dev).wait_stream(self._comm)
+            self._allreduce_on_comm(self._flat[lo:hi])
+        torch.cuda.current_stream(self._flat.device).wait_stream(self._comm)
 
     def _opt_step(self):
         """The optimizer step.  FusedAdamW clips and schedules on the device; for torch.optim.AdamW
@@ -865,9 +854,6 @@ class TrainStep:
         if self._g is not None or self._g_opt is not None:
             torch.cuda.synchronize()
         self._g = self._g_opt = None
-        if self.collective == "overlap":
-            from . import ops
-            ops.set_sink_listener(None)
         if dist.is_initialized():
             for attr in ("_cpg", "_flag_pg"):
                 if getattr(self, attr) is not None:
@@ -896,7 +882,7 @@ class TrainStep:
         if labels.data_ptr() != self._labels.data_ptr():
             self._labels.copy_(labels)
         if isinstance(self.opt, FusedAdamW):
-            self.opt.refresh_if_stale()
+            self.opt.refresh_casts(only_if_stale=True)
         self._g.replay()
         if self._g_opt is not None:
             if self._flagged:

@@ -121,7 +121,7 @@ class EncoderBlock(nn.Module):
 
 def encoder_weight_groups(blocks):
     """Column-block groups of every Dense kernel of the blocks (attention QKV / output projection,
-    FF Dense_0 / Dense_1) for ``ops.cast_weights``."""
+    FF Dense_0 / Dense_1) for ``ops.forward_casts``."""
     groups = []
     for blk in blocks:
         groups += blk.SelfAttentionBlock_0.weight_groups()
@@ -159,8 +159,7 @@ class Encoder(nn.Module):
             # Same math as vit.py:19-31,57, with every residual add fused into the LayerNorm that
             # follows it (the next block's LayerNorm_0, or the final one): one HBM pass each; every
             # Dense kernel of the encoder cast to bf16 in one launch up front.
-            ops.cast_weights(encoder_weight_groups(blocks))
-            try:
+            with ops.forward_casts(encoder_weight_groups(blocks)):
                 # (x, h): the residual gradient is added inside the LayerNorm backward kernel
                 x, h = ops.layer_norm_pass(x, blocks[0].LayerNorm_0.scale, blocks[0].LayerNorm_0.bias)
                 for i, blk in enumerate(blocks):
@@ -178,8 +177,6 @@ class Encoder(nn.Module):
                     else:
                         x, h = ops.add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias,
                                                   dropout=drop)
-            finally:
-                ops.clear_weight_cache()
             return h
         for blk in blocks:
             x = blk(x, is_training)

@@ -181,6 +181,7 @@ def test_aliased_transform_bucket_waits_for_accumulation(tmp_path):
     final when dT1's sink is written -- autograd still adds dT2.  With the fix neither is sunk and
     the post-accumulate hook releases the bucket; the 2-rank result equals the single process."""
     from sae_vision_amd import ops, train
+    from sae_vision_amd.sinks import GradSinks
     out = str(tmp_path / "alias.pt")
     mp.spawn(_alias_worker, args=(2, _free_port(), out), nprocs=2, join=True)
     got = torch.load(out, weights_only=True)
@@ -192,20 +193,12 @@ def test_aliased_transform_bucket_waits_for_accumulation(tmp_path):
     flat = torch.cat([p.detach().flatten() for p in ref.model.parameters()])
     torch.testing.assert_close(got["params"][0], flat, rtol=1e-5, atol=1e-6)
     # the sink decision itself: one parameter as both transforms -> neither sunk
-    p = torch.nn.Parameter(torch.zeros(4, 4))
-    p.grad = torch.zeros(4, 4)
-    ops.set_grad_sinks([p], [p.grad])
-    ops.begin_backward_sinks()
-    try:
+    p, q = (torch.nn.Parameter(torch.zeros(4, 4)) for _ in range(2))
+    p.grad, q.grad = torch.zeros(4, 4), torch.zeros(4, 4)
+    with GradSinks([p, q], [p.grad, q.grad]).backward():
         assert ops._th_sinks(p, p) == (None, None)
-        q = torch.nn.Parameter(torch.zeros(4, 4))
-        q.grad = torch.zeros(4, 4)
-        ops.set_grad_sinks([q], [q.grad])
         s1, s2 = ops._th_sinks(p, q)
         assert s1 is not None and s2 is not None
-    finally:
-        ops.end_backward_sinks()
-        ops.set_grad_sinks(None)
 
 
 def _capture_fail_worker(rank, world, port, out):

@@ -316,14 +316,13 @@ def test_graph_step_with_dropout_matches_eager(dev):
         assert a != b, (lg, lf)
     for s in (s_e, s_g, s_f):
         s.close()
-    ops.set_grad_sinks(None)
 
 
 def test_rate_zero_step_is_unchanged(dev):
     """A rate-0 model takes the step it always took: no dropout state, no extra launch, and the
     model built through the new keyword steps bit for bit like the one built without it."""
     import torch
-    from sae_vision_amd import ops, train, vit
+    from sae_vision_amd import train, vit
     losses, params = [], []
     for kw in ({}, {"attn_dropout_rate": 0.0}):
         torch.manual_seed(0)
@@ -333,6 +332,5 @@ def test_rate_zero_step_is_unchanged(dev):
         losses.append([s(x, y).clone() for x, y in _data(dev, 2)])
         params.append([p.detach().clone() for p in m.parameters()])
         s.close()
-        ops.set_grad_sinks(None)
     assert all(torch.equal(a, b) for a, b in zip(*losses))
     assert all(torch.equal(a, b) for a, b in zip(*params))

@@ -193,8 +193,7 @@ def test_cast_weights_multi_exact(dev):
     ws += [[torch.randn(96, 40, device=dev, generator=g)] for _ in range(60)]   # > one launch of items
     ws += [[torch.randn(30, 37, device=dev, generator=g)], [torch.randn(130, 68, device=dev, generator=g)]]
     # (30 x 37: the element-wise 32 x 32 path; 130 x 68: 64 x 64 vector tiles with ragged edges)
-    ops.cast_weights(ws)
-    try:
+    with ops.forward_casts(ws):
         w16, wt16 = ops._cast_lookup(ws[0])
         ref = torch.stack((wq, wk, wv), dim=1).reshape(C, 3 * H * D)
         assert torch.equal(w16, ref.to(torch.bfloat16))
@@ -204,8 +203,6 @@ def test_cast_weights_multi_exact(dev):
             assert torch.equal(a, grp[0].to(torch.bfloat16)) and torch.equal(b, grp[0].t().to(torch.bfloat16))
         wq.add_(1.0)                                   # in-place update: the entry is stale
         assert ops._cast_lookup(ws[0]) is None
-    finally:
-        ops.clear_weight_cache()
     assert ops._cast_lookup(ws[1]) is None
 
 

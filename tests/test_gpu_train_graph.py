@@ -48,11 +48,11 @@ def test_graph_step_matches_eager(dev, model, split):
 
 @pytest.mark.parametrize("model", ["deit_ti_patch16", "cait"])
 def test_flat_grad_sinks_bitwise(dev, model):
-    """The multi-rank step's in-place gradient sinks (ops.set_grad_sinks: the backward kernels write
+    """The multi-rank step's in-place gradient sinks (sinks.GradSinks: the backward kernels write
     every Dense / FF / LayerNorm / patch-embedding gradient straight into its view of the flat
     buffer) give the same gradient bits as autograd's own accumulation, and a parameter
     feeding two sink-writing ops in one backward is refused."""
-    from sae_vision_amd import cait, ops, train, vit
+    from sae_vision_amd import cait, train, vit
     torch.manual_seed(0)
     if model == "cait":
         m_a = cait.create_cait("cait_xxs_24", 1000, torch.bfloat16, stoch_depth=False, device=dev)
@@ -79,14 +79,10 @@ def test_flat_grad_sinks_bitwise(dev, model):
     for (n, p), g in zip(m_b.named_parameters(), g1):
         assert torch.allclose(p.grad, 2 * g, rtol=1e-5, atol=1e-6), n
     # inside one window a parameter's sink can be written once: a second backward is refused
-    ops.begin_backward_sinks()
-    try:
+    with s_b._sinks.backward():
         train.smoothed_cross_entropy(m_b(x, is_training=True), y).backward()
         with pytest.raises(RuntimeError, match="written twice"):
             train.smoothed_cross_entropy(m_b(x, is_training=True), y).backward()
-    finally:
-        ops.end_backward_sinks()
-    ops.set_grad_sinks(None)
 
 
 def test_fused_adamw_matches_torch(dev):
@@ -124,7 +120,8 @@ def test_fused_adamw_matches_torch(dev):
 def test_grad_sink_follows_param_grad(dev):
     """A sink is only used while it is still the parameter's .grad: after the gradient is reset
     (zero_grad(set_to_none=True)) autograd's own accumulation takes over again."""
-    from sae_vision_amd import ops, vit
+    from sae_vision_amd import vit
+    from sae_vision_amd.sinks import GradSinks
     torch.manual_seed(0)
     m = vit.create_model("deit_ti_patch16", 1000, torch.bfloat16, device=dev)
     params = [p for p in m.parameters()]
@@ -133,18 +130,54 @@ def test_grad_sink_follows_param_grad(dev):
     for p in params:
         p.grad = flat[off:off + p.numel()].view_as(p)
         off += p.numel()
-    ops.set_grad_sinks(params, [p.grad for p in params])
+    sinks = GradSinks(params, [p.grad for p in params])
     for p in params:
         p.grad = None            # reset: the registered views are no longer the gradients
-    ops.begin_backward_sinks()
-    try:
+    with sinks.backward():
         x = torch.randn(2, 224, 224, 3, device=dev)
         m(x, is_training=True).float().sum().backward()
-    finally:
-        ops.end_backward_sinks()
     assert all(p.grad is not None for p in params)
     assert float(flat.abs().max()) == 0.0   # nothing went into the stale views
-    ops.set_grad_sinks(None)
+
+
+def test_two_sink_sets_interleaved(dev):
+    """Two independent parameter sets, each with its own flat buffer and its own GradSinks, run in
+    turn (A, B, A again after zeroing): a window sinks its own set's gradients and nothing else.
+    Every gradient equals, bit for bit, the same graph run with no sinks, and the other set's
+    buffer is left as it was.  16 rows x 64 columns is the smallest shape that takes the
+    sae_gemm_dw and LayerNorm-backward sink paths."""
+    from sae_vision_amd import ops, train
+    from sae_vision_amd.sinks import GradSinks
+    g = torch.Generator(device=dev).manual_seed(29)
+    rand = lambda *s: torch.randn(*s, device=dev, generator=g)
+    x = rand(2, 8, 64)
+
+    def run(ps):
+        W, b, gamma, beta = ps
+        ops.dense(ops.layer_norm(x, gamma, beta), W, b, torch.bfloat16).float().sum().backward()
+
+    def make():
+        ps = [t.requires_grad_() for t in (rand(64, 64) / 8, rand(64) * 0.1, 1 + rand(64) * 0.1, rand(64) * 0.1)]
+        ref = [p.detach().clone().requires_grad_() for p in ps]
+        run(ref)                                          # the same graph, no sinks: autograd's gradients
+        offs, n = train.flat_layout(ps)
+        flat = torch.zeros(n, device=dev)
+        for p, o in zip(ps, offs):
+            p.grad = flat[o:o + p.numel()].view_as(p)
+        return ps, flat, GradSinks(ps, [p.grad for p in ps]), [r.grad for r in ref]
+
+    pa, fa, sa, ra = make()
+    pb, fb, sb, rb = make()
+    for ps, flat, sinks, ref, other in ((pa, fa, sa, ra, fb), (pb, fb, sb, rb, fa), (pa, fa, sa, ra, fb)):
+        flat.zero_()
+        before = other.clone()
+        with sinks.backward():
+            run(ps)
+        torch.cuda.synchronize()
+        assert sinks.written == {p.grad.data_ptr() for p in ps}      # all four went through their sinks
+        for p, r in zip(ps, ref):
+            assert p.grad.data_ptr() >= flat.data_ptr() and torch.equal(p.grad, r)
+        assert torch.equal(other, before)                            # nothing written into the other set's buffer
 
 
 @pytest.mark.parametrize("flagged", ["1", "0"])
@@ -214,7 +247,7 @@ def test_fused_adamw_cast_copies(dev):
         assert torch.equal(w16, b[2].detach().to(torch.bfloat16))
     finally:
         opt_b.close()
-    assert ops._wkey([b[2]]) not in ops._PERSIST
+    assert ops._cast_lookup([b[2]]) is None
     # a parameter named by two groups is updated once: the second group is left to the forward
     c, fc = make()
     opt_c = train.FusedAdamW(c, fc, cast_groups=[[c[2]], [c[2]], [c[0], c[0]]], **kw)

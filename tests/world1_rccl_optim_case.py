@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 def main(model):
     import torch
     import torch.distributed as dist
-    from sae_vision_amd import ops, train, vit
+    from sae_vision_amd import train, vit
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     m_a = vit.create_model(model, 1000, torch.bfloat16, device=dev)
@@ -69,7 +69,6 @@ def main(model):
             s_b.close()
         s_a.close()
         dist.destroy_process_group()
-        ops.set_sink_listener(None)
     print("WORLD1_OPTIM_OK", flush=True)
 
 
