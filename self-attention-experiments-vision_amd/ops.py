@@ -6,13 +6,8 @@ strides, and calls the HIP library on the current stream.  Forward saves the log
 rows, never the [B, H, Nq, Nk] probabilities (the reference materialises them:
 models/layers/attentions/attention.py:41-58).
 
-Public functions
-  attention(q, k, v, scale, bias=None)         core of AttentionBlock (attention.py:39-58)
-  attention_packed(qkv, scale)                  same, q/k/v packed [B, N, 3, H, D] (one buffer,
-                                                one gradient buffer, no copies)
-  talking_heads_attention(q, k, v, th1, th2, scale)   attention.py:41-52 with talking_heads
-  relpos_bias(qhat, emb_h, emb_w, grid)         BoTNet RelativeLogits tables (botnet.py:70-141)
-  rotary(x, base=10000.)                        rotary embedding (position_embed.py:8-20)
+The public functions are the names in ``__all__``; each one's docstring cites the reference lines it
+restates.  A Dense projection's routes are planned by ``dense_fwd_plan`` / ``dense_bwd_plan``.
 """
 from __future__ import annotations
 
@@ -22,14 +17,17 @@ import dataclasses
 import functools
 import math
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _lib as L
 
-__all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "weight_cast", "forward_casts", "clear_weight_cache", "gemm_dw", "layer_norm", "add_layer_norm", "dropout_rows", "dropout_rows_mask", "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed", "relpos_bias", "rotary",
-           "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer"]
+__all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "weight_cast", "forward_casts",
+           "clear_weight_cache", "gemm_dw", "layer_norm", "add_layer_norm", "dropout_rows", "dropout_rows_mask",
+           "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed",
+           "relpos_bias", "rotary", "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer",
+           "DenseFacts", "dense_facts_of_shapes", "dense_fwd_plan", "dense_bwd_plan"]
 
 
 class KernelTimer:
@@ -809,10 +807,27 @@ def _f32_operand_ok(t: torch.Tensor) -> bool:
     return False
 
 
+def _rows_ok(t: torch.Tensor) -> bool:
+    """A 2-D operand sae_gemm_nt / sae_gemm_dw read in place: bf16 on the GPU, unit column stride,
+    width and row pitch multiples of 8, 16-byte aligned."""
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.shape[1] % 8 == 0 and t.stride(1) == 1
+            and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _nt_ok(a2: torch.Tensor, N: int) -> bool:
+    return N % 8 == 0 and _rows_ok(a2)
+
+
 def _dw_ok(x2: torch.Tensor, dy2: torch.Tensor) -> bool:
-    return (x2.is_cuda and x2.dtype == dy2.dtype == torch.bfloat16 and x2.shape[1] % 8 == 0 and dy2.shape[1] % 8 == 0
-            and x2.stride(1) == 1 and dy2.stride(1) == 1 and x2.stride(0) % 8 == 0 and dy2.stride(0) % 8 == 0
-            and x2.data_ptr() % 16 == 0 and dy2.data_ptr() % 16 == 0)
+    return _rows_ok(x2) and _rows_ok(dy2)
+
+
+def _pitched(t: torch.Tensor, align: bool = True) -> torch.Tensor:
+    """``t`` [M, K] with a unit column stride, a row pitch that is a multiple of 8 elements and
+    (``align``) a 16-byte-aligned base, as the GEMM kernels read it in place: copied only if it is not."""
+    if t.stride(1) != 1 or t.stride(0) % 8 or (align and t.data_ptr() % 16):
+        return t.contiguous()
+    return t
 
 
 # ------------------------------------------------------------ registry of the bf16 weight copies
@@ -949,115 +964,219 @@ def _cast(ws, dt):
     return w.to(dt), None
 
 
+# ------------------------------------------------------------- Dense: facts, plans, executors
+# Every bf16 projection on aligned operands whose widths are multiples of 8 runs forward and input gradient
+# on sae_gemm_nt (the C ABI picks the kernel: gemm.hip nt_plan) and its weight gradient on sae_gemm_dw: every
+# width in create_model.py:6-215 (ViT-B/L, DeiT, CaiT 192-768, CeiT, CvT 64/192/368/1024, TNT 24/40/384/640);
+# tests/test_routing_cpu.py pins it on the plans below.  GEMM_LIB = True sends forward and input gradient to
+# the library GEMM (A/B runs only).
+GEMM_LIB = False
+# Calls of at most SMALL_M rows (classifier heads, CLS-token projections): while GEMM_LIB is on they keep
+# their forward on sae_gemm_nt (with it off the bound decides nothing there), and only they take "dw_t".
+SMALL_M = 4096
+
+
+class DenseFacts(NamedTuple):
+    """What the route of one Dense call depends on.  The layout fields are the results of _nt_ok /
+    _dw_ok / _f32_operand_ok (false off the GPU); the three about dY are known in the backward only."""
+    M: int                 # rows
+    I: int                 # input features
+    widths: tuple          # output features per column block (J = their sum)
+    dtype: torch.dtype     # compute dtype
+    on_gpu: bool
+    nt_x: bool             # x2 is an sae_gemm_nt operand for J output features
+    nt_dy: bool            # dy2 ... for I output features
+    dw: bool               # x2 and dy2 are sae_gemm_dw operands
+    dw_t: bool             # J % 8 != 0 (no sae_gemm_nt), and a fresh dY^T [J, M] and the bf16 W^T [J, I] are
+    f32_x: bool            # x2 and W are sae_gemm_f32 operands
+    f32_dy: bool           # dy2 is
+    has_wt: bool           # a bf16 W^T exists
+    has_bias: bool
+    sinks_w: tuple         # per column block: its kernel has a gradient sink
+    sink_b: bool
+    adjacent: bool         # every block has a sink and they lie back to back: one [nb, I, n] buffer
+    gemm_lib: bool         # GEMM_LIB
+
+
+def _dense_facts(x2, wd, wt, has_bias, sw, sb, widths) -> DenseFacts:
+    """The facts of a call from its tensors, as the forward knows them (dY: see _Dense.backward)."""
+    (M, I), J = x2.shape, wd.shape[1]
+    adjacent = sw[0] is not None and (len(sw) == 1 or all(   # (read for equal-width blocks only)
+        t is not None and t.data_ptr() == sw[0].data_ptr() + k * I * widths[0] * 4 for k, t in enumerate(sw)))
+    # dY has y's dtype and device and M rows, so its contiguous transpose [J, M] (J > 1: a fresh,
+    # allocator-aligned copy of pitch M) is an sae_gemm_dw operand exactly when M % 8 == 0
+    dw_t = wt is not None and J % 8 != 0 and J > 1 and M % 8 == 0 and _rows_ok(wt)
+    f32_x = wd.dtype == torch.float32 and _f32_operand_ok(x2) and _f32_operand_ok(wd)
+    return DenseFacts(M, I, widths, wd.dtype, x2.is_cuda, nt_x=_nt_ok(x2, J), nt_dy=False, dw=False, dw_t=dw_t,
+                      f32_x=f32_x, f32_dy=False, has_wt=wt is not None, has_bias=has_bias,
+                      sinks_w=tuple(t is not None for t in sw), sink_b=sb is not None, adjacent=adjacent,
+                      gemm_lib=GEMM_LIB)
+
+
+def dense_facts_of_shapes(M, I, widths, dtype=torch.bfloat16, has_bias=True, sinks_w=None, sink_b=False,
+                          adjacent=True, on_gpu=True) -> DenseFacts:
+    """The facts of a call on contiguous, aligned operands with fp32 parameters and a contiguous dY (what a
+    model's Dense sees), from shapes alone.  ``adjacent``: the sinks, if every block has one, lie back to back."""
+    J = sum(widths)
+    sinks_w = tuple(sinks_w) if sinks_w is not None else (False,) * len(widths)
+    rows = on_gpu and dtype == torch.bfloat16 and I % 8 == 0   # x2 [M, I] and W^T [J, I] are row operands
+    nt = rows and J % 8 == 0
+    f32 = on_gpu and dtype == torch.float32 and J % 4 == 0
+    return DenseFacts(M, I, tuple(widths), dtype, on_gpu, nt_x=nt, nt_dy=nt, dw=nt,
+                      dw_t=rows and J % 8 != 0 and J > 1 and M % 8 == 0, f32_x=f32 and I % 4 == 0, f32_dy=f32,
+                      has_wt=on_gpu and dtype == torch.bfloat16, has_bias=has_bias, sinks_w=sinks_w,
+                      sink_b=sink_b, adjacent=adjacent and all(sinks_w), gemm_lib=GEMM_LIB)
+
+
+def _dx_reads_wt(f: DenseFacts) -> bool:
+    """The "dw_t" input gradient can run (so the forward keeps the bf16 W^T for it): a small-M call whose J is
+    no multiple of 8 (a classifier head of e.g. 10 classes), which sae_gemm_nt cannot reduce over."""
+    return f.dw_t and f.M <= SMALL_M
+
+
+def dense_fwd_plan(f: DenseFacts):
+    """(route, keep_wt): "f32" exact fp32 on sae_gemm_f32, "nt" sae_gemm_nt, "lib" the library GEMM;
+    ``keep_wt``: save the bf16 W^T for the backward."""
+    if f.f32_x:
+        route = "f32"
+    elif f.has_wt and f.nt_x and (not f.gemm_lib or f.M <= SMALL_M):
+        route = "nt"
+    else:
+        route = "lib"
+    return route, _dx_reads_wt(f)
+
+
+def dense_bwd_plan(f: DenseFacts):
+    """(dx, dw, offload).  dx: "f32", "nt", "dw_t" (sae_gemm_dw over the rows of dY^T and W^T), "lib".
+    dw: "f32"; on sae_gemm_dw "dw_blocks_sunk" (equal-width blocks, adjacent sinks: one blocked launch into
+    the first), "dw_blocks" (equal-width blocks into a fresh [nb, I, n]), "dw_sunk" (one kernel into its
+    sink), "dw" (one kernel, fresh buffer), "dw_stacked" (unequal blocks: a fresh [I, J], then slices);
+    "lib".  ``offload``: the launch writes sinks only, so it may run on the weight-gradient side stream."""
+    if f.f32_x and f.f32_dy:
+        return "f32", "f32", False
+    if f.dtype == torch.bfloat16 and f.nt_dy and not f.gemm_lib:
+        dx = "nt"
+    else:
+        dx = "dw_t" if _dx_reads_wt(f) else "lib"
+    nb, n = len(f.widths), f.widths[0]
+    if not f.dw:
+        dw = "lib"
+    elif nb == 1:
+        dw = "dw_sunk" if f.sinks_w[0] else "dw"
+    elif len(set(f.widths)) == 1 and n % 4 == 0:   # one contiguous [I, n] gradient per block: no slice copies
+        dw = "dw_blocks_sunk" if f.adjacent else "dw_blocks"
+    else:
+        dw = "dw_stacked"
+    return dx, dw, dw in ("dw_sunk", "dw_blocks_sunk") and (f.sink_b or not f.has_bias)
+
+
+def _dx_dw_t(dy2, wd, wt):
+    # the reduction runs over the ROWS of dY^T [J, M] and W^T [J, I], i.e. on the weight-gradient
+    # kernel: dx[m][i] = sum_j dY^T[j][m] W^T[j][i], fp32 then the activation dtype
+    dxf = torch.empty((dy2.shape[0], wd.shape[0]), dtype=torch.float32, device=dy2.device)
+    gemm_dw(dy2.t().contiguous(), wt, dxf)
+    return dxf
+
+
+_DX = {"f32": lambda dy2, wd, wt: gemm_f32(dy2, wd.t()), "nt": lambda dy2, wd, wt: gemm_nt(dy2, wd),
+       "dw_t": _dx_dw_t, "lib": lambda dy2, wd, wt: dy2 @ wd.t()}
+
+
+# A weight-gradient executor returns (db, [dW per column block]) as autograd sees them: None for a
+# gradient that went into its sink (flat-buffer sinks of the multi-rank step, written in place).
+def _db_out(ctx, dy2, sink):
+    return _grad_out(sink, (dy2.shape[1],), dy2.device) if ctx.has_b else None
+
+
+def _col_blocks(ctx, dw):
+    return [g.to(wdt) for g, (_, wdt) in zip(dw.split([n for n, _ in ctx.wmeta], dim=1), ctx.wmeta)]
+
+
+def _dw_f32(ctx, x2, dy2, offload):
+    # per column block dW_k = X^T dY[:, block], that block's db slice as the ones-row column sum
+    db = _db_out(ctx, dy2, ctx.sink_b)
+    dws, col = [], 0
+    for (n, wdt), sw in zip(ctx.wmeta, ctx.sinks_w):
+        dst = _grad_out(sw, (x2.shape[1], n), x2.device)
+        dyb = dy2[:, col:col + n]
+        if not _f32_operand_ok(dyb):
+            dyb = dyb.contiguous()
+        gemm_f32(x2.t(), dyb, out=dst, colsum=db[col:col + n] if db is not None else None)
+        dws.append(None if sw is not None else dst.to(wdt))
+        col += n
+    return _unsunk(db, ctx.sink_b), dws
+
+
+def _dw_blocks(ctx, x2, dy2, offload, sunk=False):
+    nb, n, I = len(ctx.wmeta), ctx.wmeta[0][0], x2.shape[1]
+    db = _db_out(ctx, dy2, ctx.sink_b)
+    if sunk:
+        for t in ctx.sinks_w:
+            _claim(t)
+        dwb = ctx.sinks_w[0].as_strided((nb, I, n), (I * n, n, 1))
+    else:
+        dwb = _grad_out(None, (nb, I, n), x2.device)
+    gemm_dw(x2, dy2, dwb, db, jblock=n, offload=offload)
+    return _unsunk(db, ctx.sink_b), [None] * nb if sunk else [dwb[k].to(wdt) for k, (_, wdt) in enumerate(ctx.wmeta)]
+
+
+def _dw_whole(ctx, x2, dy2, offload, sunk=False, bias_sink=True):
+    # "dw_stacked" (bias_sink False) writes db into a fresh buffer although the bias may have a sink:
+    # autograd then adds it into the sink.  Kept as found (DESIGN.md, open questions).
+    sb = ctx.sink_b if bias_sink else None
+    db = _db_out(ctx, dy2, sb)
+    dw = _claim(ctx.sinks_w[0]) if sunk else _grad_out(None, (x2.shape[1], dy2.shape[1]), x2.device)
+    gemm_dw(x2, dy2, dw, db, offload=offload)
+    return _unsunk(db, sb), [None] if sunk else _col_blocks(ctx, dw)
+
+
+def _dw_lib(ctx, x2, dy2, offload):
+    dw = (x2.t() @ dy2).float()
+    return dy2.sum(0, dtype=torch.float32) if ctx.has_b else None, _col_blocks(ctx, dw)
+
+
+_DW = {"f32": _dw_f32, "dw_blocks_sunk": functools.partial(_dw_blocks, sunk=True), "dw_blocks": _dw_blocks,
+       "dw_sunk": functools.partial(_dw_whole, sunk=True), "dw": _dw_whole,
+       "dw_stacked": functools.partial(_dw_whole, bias_sink=False), "lib": _dw_lib}
+
+
 class _Dense(torch.autograd.Function):
     """y = x @ W (+ b): Flax ``Dense`` / ``DenseGeneral`` semantics (input and fp32 kernel cast to
     the compute dtype).  ``W`` may be given as column blocks (the queries / keys / values kernels of
-    one stacked projection): their gradients come back as the matching column slices.  Backward:
-    dX = dY W^T, dW / db straight into fp32 by the split-token MFMA kernel (``sae_gemm_dw``) when
-    the compute dtype is bf16."""
+    one stacked projection): their gradients come back as the matching column slices.  The routes of
+    forward, dX = dY W^T and dW / db (fp32) are named by dense_fwd_plan / dense_bwd_plan."""
 
     @staticmethod
     def forward(ctx, x, b, dt, *ws):
-        I = ws[0].shape[0]
-        J = sum(w.shape[1] for w in ws)
-        x2 = x.to(dt).reshape(-1, I)
+        x2 = x.to(dt).reshape(-1, ws[0].shape[0])
         wd, wt = _cast(ws, dt)
-        if dt == torch.float32 and _f32_operand_ok(x2) and _f32_operand_ok(wd):
+        widths = tuple(w.shape[1] for w in ws)
+        ctx.wmeta = [(w.shape[1], w.dtype) for w in ws]
+        ctx.sinks_w, ctx.sink_b = [_sink(w) for w in ws], _sink(b)
+        ctx.facts = f = _dense_facts(x2, wd, wt, b is not None, ctx.sinks_w, ctx.sink_b, widths)
+        route, keep_wt = dense_fwd_plan(f)
+        if route == "f32":
             y = gemm_f32(x2, wd, b)                       # exact fp32 on the f32 MFMA, bias in the epilogue
-        elif wt is not None and (use_gemm_nt(I, J) or x2.shape[0] <= SMALL_M) and _nt_ok(x2, J):
+        elif route == "nt":
             y = gemm_nt(x2, wt, b)                        # bias in the epilogue
         else:
             # bias rides in the library GEMM's epilogue (addmm) instead of a separate pass
             y = torch.addmm(b.to(dt), x2, wd) if b is not None else x2 @ wd
-        # bf16 W^T [J, I] is kept only for the one input gradient that reads it (below: a small-M
-        # call whose J is not a multiple of 8), through save_for_backward (version-checked)
-        keep_wt = wt is not None and J % 8 != 0 and x2.shape[0] <= SMALL_M
-        ctx.save_for_backward(x2, wd, wt if keep_wt else None)
+        ctx.save_for_backward(x2, wd, wt if keep_wt else None)   # version-checked
         ctx.has_b, ctx.xshape, ctx.xdtype = b is not None, x.shape, x.dtype
-        ctx.wmeta = [(w.shape[1], w.dtype) for w in ws]
-        ctx.sinks_w, ctx.sink_b = [_sink(w) for w in ws], _sink(b)
-        return y.view(*x.shape[:-1], J)
+        return y.view(*x.shape[:-1], wd.shape[1])
 
     @staticmethod
     @_sinking
     def backward(ctx, dy):
         x2, wd, wt = ctx.saved_tensors
         I, J = wd.shape
-        dy2 = dy.reshape(-1, J)
-        if dy2.stride(1) != 1 or dy2.stride(0) % 8:
-            dy2 = dy2.contiguous()
-        if wd.dtype == torch.float32 and _f32_operand_ok(dy2) and _f32_operand_ok(x2) and _f32_operand_ok(wd):
-            return _Dense._backward_f32(ctx, x2, wd, dy2)
-        if use_gemm_nt(J, I) and _nt_ok(dy2, I) and wd.dtype == torch.bfloat16:
-            dx = gemm_nt(dy2, wd).view(ctx.xshape).to(ctx.xdtype)
-        else:
-            dyt = dy2.t().contiguous() if (wd.dtype == torch.bfloat16 and wt is not None) else None
-            if dyt is not None and _dw_ok(dyt, wt):
-                # K = J not a multiple of 8 (a classifier head with e.g. 10 classes) -- the reduction
-                # runs over the ROWS of dY^T [J, M] and W^T [J, I], i.e. on the weight-gradient
-                # kernel: dx[m][i] = sum_j dY^T[j][m] W^T[j][i], fp32 then the activation dtype
-                dxf = torch.empty((dy2.shape[0], I), dtype=torch.float32, device=dy2.device)
-                gemm_dw(dyt, wt, dxf)
-                dx = dxf.view(ctx.xshape).to(ctx.xdtype)
-            else:
-                dx = (dy2 @ wd.t()).view(ctx.xshape).to(ctx.xdtype)
-        widths = [n for n, _ in ctx.wmeta]
-        blocked = len(widths) > 1 and len(set(widths)) == 1 and widths[0] % 4 == 0
-        sw, sb = ctx.sinks_w, ctx.sink_b
-        if _dw_ok(x2, dy2) and (blocked or len(widths) == 1):
-            # flat-buffer sinks (multi-rank step): dW / db written in place, autograd gets None
-            db = _grad_out(sb, (J,), x2.device) if ctx.has_b else None
-            rdb = _unsunk(db, sb)
-            if blocked:   # one contiguous [I, n] gradient per column block: no slice copies
-                n = widths[0]
-                s0 = sw[0]
-                if s0 is not None and all(t is not None and t.data_ptr() == s0.data_ptr() + k * I * n * 4
-                                          for k, t in enumerate(sw)):   # adjacent sinks: one [nb, I, n] block
-                    for t in sw:
-                        _claim(t)
-                    gemm_dw(x2, dy2, s0.as_strided((len(widths), I, n), (I * n, n, 1)), db, jblock=n,
-                            offload=sb is not None or not ctx.has_b)
-                    return (dx, rdb, None, *[None] * len(widths))
-                dwb = torch.empty((len(widths), I, n), dtype=torch.float32, device=x2.device)
-                gemm_dw(x2, dy2, dwb, db, jblock=n)
-                return (dx, rdb, None, *[dwb[k].to(wdt) for k, (_, wdt) in enumerate(ctx.wmeta)])
-            if sw[0] is not None:
-                gemm_dw(x2, dy2, _claim(sw[0]), db, offload=sb is not None or not ctx.has_b)
-                return dx, rdb, None, None
-            dw = torch.empty((I, J), dtype=torch.float32, device=x2.device)
-            gemm_dw(x2, dy2, dw, db)
-            db = rdb
-        elif _dw_ok(x2, dy2):
-            dw = torch.empty((I, J), dtype=torch.float32, device=x2.device)
-            db = torch.empty((J,), dtype=torch.float32, device=x2.device) if ctx.has_b else None
-            gemm_dw(x2, dy2, dw, db)
-        else:
-            dw = (x2.t() @ dy2).float()
-            db = dy2.sum(0, dtype=torch.float32) if ctx.has_b else None
-        dws, col = [], 0
-        for n, wdt in ctx.wmeta:
-            dws.append(dw[:, col:col + n].to(wdt))
-            col += n
+        dy2 = _pitched(dy.reshape(-1, J), align=False)   # (a misaligned dY is not copied: the library routes)
+        dx_route, dw_route, offload = dense_bwd_plan(ctx.facts._replace(
+            nt_dy=_nt_ok(dy2, I), dw=_dw_ok(x2, dy2), f32_dy=_f32_operand_ok(dy2)))
+        dx = _DX[dx_route](dy2, wd, wt).view(ctx.xshape).to(ctx.xdtype)
+        db, dws = _DW[dw_route](ctx, x2, dy2, offload)
         return (dx, db, None, *dws)
-
-    @staticmethod
-    def _backward_f32(ctx, x2, wd, dy2):
-        """fp32 compute dtype: dX = dY W^T, then per column block dW_k = X^T dY[:, block] with that
-        block's db slice as the ones-row column sum, all on sae_gemm_f32; sinks written in place."""
-        I, J = wd.shape
-        dx = gemm_f32(dy2, wd.t()).view(ctx.xshape).to(ctx.xdtype)
-        sb = ctx.sink_b
-        db = _grad_out(sb, (J,), x2.device) if ctx.has_b else None
-        dws, col = [], 0
-        for (n, wdt), sw in zip(ctx.wmeta, ctx.sinks_w):
-            dst = _grad_out(sw, (I, n), x2.device)
-            dyb = dy2[:, col:col + n]
-            if not _f32_operand_ok(dyb):
-                dyb = dyb.contiguous()
-            gemm_f32(x2.t(), dyb, out=dst, colsum=db[col:col + n] if db is not None else None)
-            dws.append(None if sw is not None else dst.to(wdt))
-            col += n
-        return (dx, _unsunk(db, sb), None, *dws)
 
 
 def dense(x: torch.Tensor, w, b: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
@@ -1179,27 +1298,6 @@ EPI_GELU_GRAD, EPI_MUL_AUX = 3, 4
 FF_GELU_GRAD = os.environ.get("SAE_FF_GELU_GRAD", "1") != "0"   # (False: save h, GELU' epilogue; A/B)
 
 
-# Every bf16 forward / input-gradient projection whose widths are multiples of 8 runs on
-# sae_gemm_nt (round 5): the C ABI picks the kernel by tile fill and reduction depth (gemm.hip nt_plan,
-# g8x_route / g8_route: the persistent gemm8, the ping-pong gemm8x, or the 128-row kernel, which
-# also takes K not a multiple of 64).  That covers every width in create_model.py:6-215 (ViT-B/L,
-# DeiT, CaiT 192-768, CeiT, CvT 64/192/368/1024, TNT 24/40/384/640); tests/test_routing_cpu.py
-# pins it.  GEMM_LIB = True sends them to the library GEMM instead (A/B runs only).
-GEMM_LIB = False
-SMALL_M = 4096   # Dense calls on at most this many rows (classifier heads, CLS-token projections)
-
-
-def use_gemm_nt(K: int, N: int) -> bool:
-    """Route a forward / input-gradient GEMM (reduction depth K, N output features) to sae_gemm_nt."""
-    return not GEMM_LIB and K % 8 == 0 and N % 8 == 0
-
-
-def _nt_ok(a2: torch.Tensor, N: int) -> bool:
-    K = a2.shape[1]
-    return (a2.is_cuda and a2.dtype == torch.bfloat16 and K % 8 == 0 and N % 8 == 0 and a2.stride(1) == 1
-            and a2.stride(0) % 8 == 0 and a2.data_ptr() % 16 == 0)
-
-
 def weight_cast(w: torch.Tensor, plain: bool = True, transposed: bool = True):
     """fp32 Dense kernel [K, N] -> (bf16 [K, N] or None, bf16 [N, K] or None) in one HIP pass."""
     lib = L.load()
@@ -1265,9 +1363,7 @@ class _FFBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w0, b0, w1, b1, drop=None):
         I, Hd = w0.shape
-        x2 = x.to(torch.bfloat16).reshape(-1, I)
-        if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
-            x2 = x2.contiguous()
+        x2 = _pitched(x.to(torch.bfloat16).reshape(-1, I))
         w0p, w0t = _cast([w0], torch.bfloat16)
         w1p, w1t = _cast([w1], torch.bfloat16)
         gg = FF_GELU_GRAD or drop is not None   # the hidden dropout rides in the saved gelu'(h)
@@ -1285,9 +1381,7 @@ class _FFBlock(torch.autograd.Function):
         x2, h, a, w0p, w1p = ctx.saved_tensors
         I, Hd = w0p.shape
         O = w1p.shape[1]
-        dy2 = dy.to(torch.bfloat16).reshape(-1, O)
-        if dy2.stride(1) != 1 or dy2.stride(0) % 8 or dy2.data_ptr() % 16:
-            dy2 = dy2.contiguous()
+        dy2 = _pitched(dy.to(torch.bfloat16).reshape(-1, O))
         dh = gemm_nt(dy2, w1p, None, EPI_MUL_AUX if ctx.gg else EPI_DGELU, aux=h)   # dA W1^T, times gelu'(h)
         sw0, sb0, sw1, sb1 = ctx.sinks   # flat-buffer sinks (multi-rank step): written in place
         dev = dy2.device

@@ -88,9 +88,10 @@ def test_dense_grads_match_autograd(dev):
 
 @pytest.mark.parametrize("rows,C", [(32, 768), (128, 384)])
 def test_classifier_head_dense(dev, rows, C):
-    """The classifier head (C -> 1000 classes: K = 1000 is no multiple of 64 in the input gradient)
-    runs on the HIP kernels: forward on sae_gemm_nt (small-M rule), dX on the weight-gradient
-    kernel over the rows of dY^T / W^T; against float64 products of the same bf16 values."""
+    """The classifier head (C -> 1000 classes: K = 1000 is a multiple of 8 but not of 64 in the input
+    gradient) runs on the HIP kernels: forward and dX on sae_gemm_nt (dX on its K-tail row), dW / db on
+    sae_gemm_dw; against float64 products of the same bf16 values.  (A class count that is no multiple
+    of 8 takes the "dw_t" route: test_small_head_dgrad_on_gemm_dw.)"""
     import sae_vision_amd.ops as ops
     g = torch.Generator(device=dev).manual_seed(rows)
     x = torch.randn(rows, C, device=dev, generator=g).to(torch.bfloat16).requires_grad_()
@@ -112,7 +113,7 @@ def test_classifier_head_dense(dev, rows, C):
 def test_small_head_dgrad_on_gemm_dw(dev, monkeypatch, rows, C, J):
     """A small-M classifier head whose class count J is not a multiple of 8 (e.g. 10 classes): the
     input gradient dX = dY W^T reduces over J, so it runs on the weight-gradient kernel over the
-    ROWS of dY^T [J, M] and the bf16 W^T [J, C] the forward saved (ops.py _Dense.backward); the
+    ROWS of dY^T [J, M] and the bf16 W^T [J, C] the forward saved (ops.py: the "dw_t" route of dense_bwd_plan); the
     test asserts that route is taken (not the library GEMM) and checks dX against float64."""
     import sae_vision_amd.ops as ops
     calls = []

@@ -2,9 +2,10 @@
 
 Every forward and input-gradient GEMM of every attention encoder width in the reference's model
 registry (models/create_model.py:6-215 -- ViT-B/L, CaiT XXS..M, CeiT, CvT, TNT inner / outer;
-plus DeiT-Ti/S of SURVEY D10) must run on this repo's ``sae_gemm_nt``: ``ops.use_gemm_nt`` sends
-it there, and ``sae_gemm_nt_route`` (the C ABI's kernel choice, include/sae_attn.h) must name a
-HIP kernel for it.  The projections are attention.py:29-37,60-63 and the FF block ff.py:8-34.
+plus DeiT-Ti/S of SURVEY D10) must run on this repo's ``sae_gemm_nt``: the Dense plans
+(``ops.dense_fwd_plan`` / ``dense_bwd_plan``) send it there, and ``sae_gemm_nt_route`` (the C ABI's
+kernel choice, include/sae_attn.h) must name a HIP kernel for it.  The projections are
+attention.py:29-37,60-63 and the FF block ff.py:8-34.
 The rocprofv3 step profiles confirm on the GPU that no library GEMM runs (profiles/)."""
 import pytest
 
@@ -54,11 +55,23 @@ def lib():
     return L.load()
 
 
+def _dense_calls(C, hidden, M):
+    # (I, column-block widths) of every ops.dense call of one encoder block, and the 1000-class head
+    return {"qkv": (M, C, (C, C, C)), "kv": (M, C, (C, C)), "oproj": (M, C, (C,)), "Dense_0": (M, C, (hidden,)),
+            "Dense_1": (M, hidden, (C,)), "head": (128, C, (1000,))}
+
+
 @pytest.mark.parametrize("name,C,hidden", WIDTHS)
 def test_every_width_routes_to_hip(lib, name, C, hidden):
     for M in (128, 197 * 32, 197 * 128):   # a classifier-head-sized call and two batch sizes
+        for what, (rows, I, widths) in _dense_calls(C, hidden, M).items():
+            f = ops.dense_facts_of_shapes(rows, I, widths)   # bf16, with a bias, no sinks
+            sunk = f._replace(sinks_w=(True,) * len(widths), sink_b=True, adjacent=True)
+            for f in (f, f._replace(has_bias=False), sunk):
+                dx, dw, _ = ops.dense_bwd_plan(f)
+                assert (ops.dense_fwd_plan(f), dx) == (("nt", False), "nt"), f"{name} {what} {f}: not on sae_gemm_nt"
+                assert dw in ("dw", "dw_sunk", "dw_blocks", "dw_blocks_sunk", "dw_stacked"), f"{name} {what} {f}: {dw}"
         for what, (K, N, epi) in _shapes(C, hidden).items():
-            assert ops.use_gemm_nt(K, N), f"{name} {what} (K={K}, N={N}) would run on the library GEMM"
             r = lib.sae_gemm_nt_route(M, N, K, epi)
             assert r != NONE, f"{name} {what} (M={M}, K={K}, N={N}) has no HIP kernel"
             assert (r == KTAIL) == (K % 64 != 0), (name, what, r)
@@ -87,7 +100,9 @@ def test_unsupported_shapes(lib):
     assert lib.sae_gemm_nt_route(1024, 1000, 12, 0) == NONE
     assert lib.sae_gemm_nt_route(1024, 10, 384, 0) == NONE
     assert lib.sae_gemm_nt_route(0, 64, 64, 0) == NONE
-    assert not ops.use_gemm_nt(12, 64) and not ops.use_gemm_nt(64, 10)
+    for I, J in ((12, 64), (64, 10)):
+        f = ops.dense_facts_of_shapes(1024, I, (J,))
+        assert ops.dense_fwd_plan(f)[0] == "lib" and ops.dense_bwd_plan(f)[0] != "nt", (I, J)
 
 
 def test_library_switch():
@@ -95,10 +110,12 @@ def test_library_switch():
     old = ops.GEMM_LIB
     try:
         ops.GEMM_LIB = True
-        assert not ops.use_gemm_nt(768, 2304)
+        f = ops.dense_facts_of_shapes(25216, 768, (2304,))
+        assert ops.dense_fwd_plan(f)[0] == "lib" and ops.dense_bwd_plan(f)[0] == "lib"
     finally:
         ops.GEMM_LIB = old
-    assert ops.use_gemm_nt(768, 2304)
+    f = ops.dense_facts_of_shapes(25216, 768, (2304,))
+    assert ops.dense_fwd_plan(f)[0] == "nt" and ops.dense_bwd_plan(f)[0] == "nt"
 
 
 # ``sae_gemm_nt_instance`` reports the row of gemm.hip's instance tables that nt_plan picks, by name

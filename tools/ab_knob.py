@@ -6,7 +6,7 @@ interleaved over rounds; median ms/step.
 
     SAE_ATTN_LIB=<pkg>/libsae_attn_dev.so python tools/ab_knob.py KNOB=v1 [KNOB=v2 ...] [--model m]
     e.g. python tools/ab_knob.py SAE_NT_NO_G8=1 SAE_NT_NO_G8=0
-         python tools/ab_knob.py ops.GEMM_LIB_WIDE=1 ops.GEMM_LIB_WIDE=0   (module flags of ops)
+         python tools/ab_knob.py ops.GEMM_LIB=1 ops.GEMM_LIB=0   (module flags of ops)
 """
 import argparse
 import copy
