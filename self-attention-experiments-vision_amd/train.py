@@ -21,6 +21,13 @@ multi-rank rehearsal on one GPU: an explicit host round trip between two graphs)
 process group).  ``SAE_WORLD1_RCCL=1`` (bench.py ``--world1-rccl``) creates a world-size-1 RCCL
 group so the overlapped collective path runs on a one-GPU box.
 
+Structure: ``step_facts`` gathers what a step's structure depends on (the process group, where
+the parameters live, the constructor's arguments, ``SAE_FLAGGED`` / ``SAE_WG_STREAM``) and
+``step_plan``, a pure function, decides it once: flat or per-parameter gradients, the optimizer,
+the collective mode, one graph or two, flag-gated or not, which process groups, streams, hooks
+and sinks exist.  ``TrainStep.__init__`` builds what the plan names.  The buckets and their
+all-reduce are a ``reducer.GradReducer`` (``TrainStep.reducer``, None without a process group).
+
 Loss: one-hot -> optax.smooth_labels(0.1) -> softmax cross-entropy, mean (train.py:83-92).
 Optimizer: the reference's chain (train.py:22-27,214-220): clip_by_global_norm(``clip_grad``),
 Adam, decoupled weight decay 1e-4, scale by the schedule.  ``lr_schedule=None`` keeps the constant
@@ -45,10 +52,11 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
+from .reducer import GradReducer, parse_emulate_rccl
 from .sinks import GradSinks
 
 __all__ = ["smoothed_cross_entropy", "TrainStep", "init_distributed", "FusedAdamW", "WarmupCosine",
-           "reference_schedule"]
+           "reference_schedule", "StepFacts", "StepPlan", "step_facts", "step_facts_of_values", "step_plan"]
 
 
 @dataclass(frozen=True)
@@ -120,8 +128,8 @@ def init_distributed():
         # RCCL (2.26 bundled with torch, 2.27 in /opt/rocm; both read NCCL_RUNTIME_CONNECT) by
         # default connects the ring / tree peers lazily, inside the first collective that needs
         # them -- for the gradient group that first collective is issued INSIDE the step's graph
-        # capture (TrainStep._cpg), where the connection setup's allocations and host handshakes
-        # would run in a capturing context.  With 0 every communicator -- the default one created
+        # capture (TrainStep.reducer.group), where the connection setup's allocations and host
+        # handshakes would run in a capturing context.  With 0 every communicator -- the default one created
         # by init_process_group(device_id=) and the gradient group's by new_group(device_id=) --
         # is fully connected when its creation returns, so the captured collectives only enqueue
         # kernels.  A value the user exported wins.
@@ -358,6 +366,108 @@ class FusedAdamW:
         return [self.m, self.v, self.step_count] + ([] if self.hyper is None else [self.hyper])
 
 
+class StepFacts(NamedTuple):
+    """What the structure of a training step depends on (``step_plan``), and nothing else."""
+    pg: bool                     # there is a default process group
+    backend: Optional[str]       # ... its backend ("nccl" / "gloo")
+    world: int
+    on_gpu: bool                 # every parameter is on the GPU
+    fp32_contiguous: bool        # every parameter is fp32 and contiguous
+    cuda: bool                   # torch.cuda.is_available()
+    graph: bool                  # the arguments of TrainStep, as given ...
+    flat_grads: Optional[bool]
+    grad_sinks: bool
+    two_graphs: Optional[bool]
+    wgrad_stream: bool           # ... (None resolved from SAE_WG_STREAM)
+    clip_or_schedule: bool       # clip_grad or lr_schedule is set
+    flagged_on: bool             # SAE_FLAGGED != "0"
+
+
+def step_facts(params, graph, flat_grads, grad_sinks, two_graphs, wgrad_stream, clip_or_schedule) -> StepFacts:
+    """The facts of a step over ``params`` from TrainStep's arguments and the live process state (the
+    default process group, the devices, SAE_FLAGGED, SAE_WG_STREAM: read here and nowhere else)."""
+    pg = dist.is_initialized()
+    if wgrad_stream is None:
+        wgrad_stream = os.environ.get("SAE_WG_STREAM", "0") == "1"
+    return StepFacts(pg=pg, backend=dist.get_backend() if pg else None, world=dist.get_world_size() if pg else 1,
+                     on_gpu=all(p.is_cuda for p in params),
+                     fp32_contiguous=all(p.dtype == torch.float32 and p.is_contiguous() for p in params),
+                     cuda=torch.cuda.is_available(), graph=bool(graph), flat_grads=flat_grads,
+                     grad_sinks=bool(grad_sinks), two_graphs=two_graphs, wgrad_stream=bool(wgrad_stream),
+                     clip_or_schedule=bool(clip_or_schedule),
+                     flagged_on=os.environ.get("SAE_FLAGGED", "1") != "0")
+
+
+def step_facts_of_values(pg=False, backend=None, world=1, on_gpu=True, fp32_contiguous=True, cuda=True, graph=True,
+                         flat_grads=None, grad_sinks=True, two_graphs=None, wgrad_stream=False,
+                         clip_or_schedule=False, flagged_on=True) -> StepFacts:
+    """The facts from plain values; the defaults are bench.py's step on one GPU (fp32 GPU parameters,
+    graph=True, no process group, no environment switch set)."""
+    return StepFacts(pg, backend, world, on_gpu, fp32_contiguous, cuda, graph, flat_grads, grad_sinks, two_graphs,
+                     wgrad_stream, clip_or_schedule, flagged_on)
+
+
+class StepPlan(NamedTuple):
+    """The structure of a training step: what TrainStep.__init__ builds and its step runs."""
+    graph: bool            # the step is captured as HIP graph(s)
+    flat: bool             # one flat gradient buffer (else per-parameter gradients)
+    fused: bool            # the one-launch FusedAdamW (else torch.optim.AdamW)
+    collective: str        # "none" | "host" | "between" | "overlap"
+    flagged: bool          # the overlapped all-reduces are flag-gated outside a linear graph (GradReducer)
+    two_graphs: bool       # forward + backward graph, optimizer graph (else one graph)
+    grad_group: bool       # create the RCCL gradient group
+    agree_group: bool      # create the gloo group of the all-ranks capture decision
+    hooks: bool            # arm the post-accumulate-grad hooks
+    comm_stream: bool      # the communication stream
+    sinks: bool            # gradient sinks
+    sink_listener: bool    # ... that tell the reducer
+    wgrad_stream: bool     # the weight-gradient side stream
+    capturable: bool       # torch.optim.AdamW(capturable=True) (read for the torch optimizer only)
+    capture_mode: str      # "thread_local" | "global"
+
+
+def step_plan(f: StepFacts) -> StepPlan:
+    """The structure of the step with facts ``f`` (pure); ValueError for the two configurations
+    TrainStep refuses."""
+    graph = f.graph and f.cuda
+    # flat gradients by default on the GPU and whenever there is a process group: written in place
+    # by the backward kernels (gradient sinks), stepped by the one-launch FusedAdamW if it can
+    flat = (f.pg or f.on_gpu) if f.flat_grads is None else bool(f.flat_grads)
+    fused = flat and f.on_gpu and f.fp32_contiguous
+    if graph and not fused and f.clip_or_schedule:
+        raise ValueError("TrainStep: clip_grad / lr_schedule with graph=True need the one-launch FusedAdamW "
+                         "(fp32 contiguous GPU parameters, flat gradients); torch.optim.AdamW applies them "
+                         "eagerly from the host")
+    if not f.pg:
+        collective = "none"
+    elif f.on_gpu and f.backend == "gloo":
+        collective = "host"
+    elif f.two_graphs:
+        collective = "between"
+    else:
+        collective = "overlap"
+    if collective != "none" and not flat:
+        raise ValueError("TrainStep: the collective path needs the flat gradient buffer")
+    overlap = collective == "overlap"
+    # flagged: the default for graph steps with the overlapped collective on the GPU; SAE_FLAGGED=0
+    # keeps the round-3 structure (the all-reduces forked inside the one graph)
+    flagged = overlap and graph and f.on_gpu and f.flagged_on
+    sinks = flat and f.grad_sinks
+    return StepPlan(
+        graph=graph, flat=flat, fused=fused, collective=collective, flagged=flagged,
+        two_graphs=collective in ("between", "host") or (collective == "none" and bool(f.two_graphs)) or flagged,
+        grad_group=(overlap or collective == "between") and f.on_gpu,
+        agree_group=f.world > 1 and graph,
+        hooks=flat and overlap, comm_stream=flat and overlap and f.on_gpu,
+        sinks=sinks, sink_listener=sinks and overlap,
+        wgrad_stream=f.wgrad_stream and sinks and f.on_gpu,
+        capturable=graph,
+        # thread_local: RCCL's watchdog thread keeps querying the events of the default group's
+        # eager work (the parameter broadcast) while the capture runs; a "global" capture would
+        # refuse those queries (hipErrorStreamCaptureUnsupported, fatal in the watchdog)
+        capture_mode="thread_local" if f.pg else "global")
+
+
 class TrainStep:
     """``step(images, labels)`` = forward (bf16 compute) + loss + backward (+ bucketed all-reduce of
     the flat gradient when there is a process group) + optimizer update.  No host sync.
@@ -388,153 +498,91 @@ class TrainStep:
         # input_layout "HWCN": the batch arrives as the reference's train-step feed [H, W, C, N]
         # (train.py:80, input_pipeline.py:187-191) and the model's patch GEMM gathers from it
         self.input_layout = input_layout
-        self.pg = dist.is_initialized()
-        self.world = dist.get_world_size() if self.pg else 1
-        self.graph = bool(graph) and torch.cuda.is_available()
-        self._g = self._g_opt = None
-        # the flat ranges _zero_grad clears (None: the whole buffer); _note_sunk narrows them
-        self._zero_ranges = None
         self.model = model
         params = [p for p in model.parameters() if p.requires_grad]
         self._params = params
+        facts = step_facts(params, graph, flat_grads, grad_sinks, two_graphs, wgrad_stream,
+                           self.clip_grad is not None or lr_schedule is not None)
+        plan = self.plan = step_plan(facts)   # (a refused configuration raises here: no collective issued yet)
+        self.pg, self.world = facts.pg, facts.world
+        self.graph, self.flat, self.collective = plan.graph, plan.flat, plan.collective
+        self._flagged, self.two_graphs = plan.flagged, plan.two_graphs
+        self._g = self._g_opt = None
+        # the flat ranges _zero_grad clears (None: the whole buffer); _note_sunk narrows them
+        self._zero_ranges = None
         if self.world > 1:
             self._broadcast_from_rank0([t for t in model.state_dict().values() if torch.is_tensor(t)])
-        # flat_grads (default: on the GPU, and whenever there is a process group): one flat gradient
-        # buffer written in place by the backward kernels (gradient sinks), stepped by the one-launch
-        # FusedAdamW
-        on_gpu = all(p.is_cuda for p in params)
-        self.flat = (self.pg or on_gpu) if flat_grads is None else bool(flat_grads)
-        # the one-launch FusedAdamW (fp32 GPU parameters in the flat buffer); torch.optim.AdamW otherwise
-        fused = self.flat and on_gpu and all(p.dtype == torch.float32 and p.is_contiguous() for p in params)
-        if self.graph and not fused and (self.clip_grad is not None or lr_schedule is not None):
-            raise ValueError("TrainStep: clip_grad / lr_schedule with graph=True need the one-launch FusedAdamW "
-                             "(fp32 contiguous GPU parameters, flat gradients); torch.optim.AdamW applies them "
-                             "eagerly from the host")
-        if not self.pg:
-            self.collective = "none"
-        elif on_gpu and dist.get_backend() == "gloo":
-            self.collective = "host"
-        elif two_graphs:
-            self.collective = "between"
-        else:
-            self.collective = "overlap"
-        if self.collective != "none" and not self.flat:
-            raise ValueError("TrainStep: the collective path needs the flat gradient buffer")
-        # the gradient all-reduces run on a process group of their own, created with an eager
-        # communicator (device_id) and given no eager work before the capture: RCCL's watchdog
-        # thread then never holds an event recorded on that group's internal stream, which joins
-        # the step's capture (an event query on a capturing stream is hipErrorCapturedEvent,
-        # fatal in the watchdog).  The warm-up steps before the capture run without collectives.
-        self._cpg = None
-        self._comm_on = True
-        # "flagged" (graph steps with the overlapped collective, default on the GPU): the captured
-        # forward + backward stays ONE linear kernel chain -- at each bucket's ready point it bumps a
-        # device flag (sae_flag_bump) instead of forking the all-reduce onto the communication stream
-        # inside the graph -- and after each replay the host enqueues, on the communication stream,
-        # every bucket's wait for its flag (hipStreamWaitValue32) followed by its RCCL all-reduce,
-        # so the rings still run beside the rest of the backward.  A branch inside a replayed HIP graph
-        # costs the whole replay 0.13-0.4 ms on this runtime (the multi-queue launch path, measured
-        # with one-rank RCCL + a stand-in kernel per bucket: profiles/r06e_graph_fork.txt,
-        # r06d_rccl_emulation.txt); a linear graph keeps the single-queue fast path.  SAE_FLAGGED=0:
-        # the round-3 structure (the all-reduces forked inside the one graph).
-        self._flagged = False
-        # one-GPU contention emulation of an N-GPU node (bench.py --emulate-rccl, env
-        # SAE_EMULATE_RCCL="channels,busbw_GBps,world[,lds_KiB[,threads]]"): beside each bucket's
-        # (one-rank) all-reduce, `channels` workgroups of `threads` threads holding `lds_KiB` of LDS
-        # (default 64 KiB, 256) occupy CUs on the communication stream for the ring time the bucket
-        # would take at `world` GPUs, 2 (world - 1) / world x bytes / busbw -- the CU footprint of
-        # RCCL's ring channels on the compute units the backward is using
-        self._emulate = None
-        em = os.environ.get("SAE_EMULATE_RCCL", "")
-        if em:
-            f = [float(x) for x in em.split(",")] + [64.0, 256.0][max(0, len(em.split(",")) - 3):]
-            self._emulate = (int(f[0]), f[1], int(f[2]), int(f[3] * 1024), int(f[4]))
-        if self.collective in ("overlap", "between") and on_gpu:
-            self._cpg = dist.new_group(backend="nccl", device_id=params[0].device)
+        dev = params[0].device
+        # the gradient all-reduces run on a process group of their own (GradReducer)
+        grad_pg = dist.new_group(backend="nccl", device_id=dev) if plan.grad_group else None
         # world > 1: whether the step runs as a graph is decided by ALL ranks together (a host-side
         # gloo group carries the one flag all-reduce): a rank whose capture fails must not run the
         # eager step while its peers replay graphs -- their collective sequences would differ
-        self._flag_pg = dist.new_group(backend="gloo") if self.world > 1 and self.graph else None
-        self._flagged = (self.collective == "overlap" and self.graph and on_gpu
-                         and os.environ.get("SAE_FLAGGED", "1") != "0")
-        self.two_graphs = (self.collective in ("between", "host") or (self.collective == "none" and bool(two_graphs))
-                           or self._flagged)
-        if self.flat:
-            # one flat fp32 gradient buffer, every .grad a 16-byte-aligned view into it (autograd
-            # accumulates into the views in place), cut into buckets of ~bucket_cap_mb along
-            # parameter boundaries in reverse registration order (the order the backward finishes
-            # them; a bucket closes once it holds >= cap elements)
-            offs, n = flat_layout(params)
-            self._offs = offs
-            dev = params[0].device
-            # zeros: the alignment padding between the views is never written by anything (the
-            # kernels and autograd write the views, _zero_grad writes zeros, a SUM all-reduce of
-            # zeros is zero), so it stays zero and the global norm may run over the whole buffer
-            self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
-            for p, off in zip(params, offs):
-                p.grad = self._flat[off:off + p.numel()].view_as(p)
-            cap = max(1, int(bucket_cap_mb * 2 ** 20 / 4))
-            self._buckets, self._bucket_params = [], []
-            hi, members = n, []
-            for i in reversed(range(len(params))):
-                members.append(i)
-                lo = offs[i]
-                if hi - lo >= cap:
-                    self._buckets.append((lo, hi))
-                    self._bucket_params.append(members)
-                    hi, members = lo, []
-            if members:
-                self._buckets.append((0, hi))
-                self._bucket_params.append(members)
-            self._bucket_of = {i: b for b, ms in enumerate(self._bucket_params) for i in ms}
-            if self.collective == "overlap":
-                self._arm_overlap_hooks()
-            if self._flagged:
-                # one int32 counter per bucket, bumped once per replay of the forward + backward graph
-                self._flags = torch.zeros(len(self._buckets), dtype=torch.int32, device=dev)
-                self._flag_order = []   # bucket order of the captured bumps (the host's issue order)
-                self._epoch = 0
+        self._flag_pg = dist.new_group(backend="gloo") if plan.agree_group else None
+        self.reducer = None
+        if plan.flat:
+            self._build_flat(dev, max(1, int(bucket_cap_mb * 2 ** 20 / 4)), grad_pg)
         # the sink-bound weight-gradient GEMMs run on a side stream beside the input-gradient chain
         # (GradSinks.wgrad_stream), opt-in: SAE_WG_STREAM=1 or wgrad_stream=True.  Off by default: the
         # concurrent dW kernels push the persistent gemm8 tiles into a tail (DeiT-S 15,381 vs
         # 15,619 img/s, profiles/r05i_wgstream_rejected.txt)
-        if wgrad_stream is None:
-            wgrad_stream = os.environ.get("SAE_WG_STREAM", "0") == "1"
-        self._wg = (torch.cuda.Stream(device=params[0].device)
-                    if wgrad_stream and self.flat and grad_sinks and on_gpu else None)
+        self._wg = torch.cuda.Stream(device=dev) if plan.wgrad_stream else None
         # the backward kernels write each parameter's gradient straight into its flat view (this step's
         # GradSinks, live inside _fwd_bwd's window) instead of autograd adding a fresh tensor into it
         self._sinks = None
-        if self.flat and grad_sinks:
+        if plan.sinks:
             self._sinks = GradSinks(params, [p.grad for p in params], wgrad_stream=self._wg,
-                                    listener=self._on_sink if self.collective == "overlap" else None)
-        base_lr = lr * (global_batch / 512)
-        kw = dict(lr=base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay)
-        self.opt = None
-        if fused:
-            # the bf16 Dense copies written by the update (models that name them, bf16 compute)
-            groups = model.cast_groups() if persistent_casts and hasattr(model, "cast_groups") else None
-            self.opt = FusedAdamW(params, self._flat, cast_groups=groups, clip_grad=self.clip_grad,
-                                  lr_schedule=lr_schedule, **kw)
-        else:
-            # the torch optimizer: clip and schedule in torch ops before its step (_opt_step)
-            self._count = 0
-            self._lr_now = self._grad_norm = None
-            if self.graph:
-                kw["capturable"] = True   # step counters on the device: replayable
-            try:
-                self.opt = torch.optim.AdamW(params, fused=True, **kw)
-            except (RuntimeError, TypeError):
-                self.opt = torch.optim.AdamW(params, foreach=True, **kw)
+                                    listener=self.reducer.on_sink if plan.sink_listener else None)
+        self.opt = self._build_optimizer(lr * (global_batch / 512), weight_decay, persistent_casts)
         self.smoothing = label_smoothing
         # dropout (attn_dropout_rate > 0 or dropout_rate > 0 on any module): the first operation
         # of each step bumps the device offset of the dropout state (ops.DropoutRng.advance), so
         # every step -- every replay of the captured graph included -- draws fresh masks.  With
         # rate 0 everywhere the step launches nothing for it.
         self._drop_rng = None
-        if on_gpu and any(getattr(m, "attn_dropout_rate", 0.0) > 0.0 or getattr(m, "dropout_rate", 0.0) > 0.0
-                          for m in model.modules()):
-            self._drop_rng = ops.dropout_rng(params[0].device)
+        if facts.on_gpu and any(getattr(m, "attn_dropout_rate", 0.0) > 0.0 or getattr(m, "dropout_rate", 0.0) > 0.0
+                                for m in model.modules()):
+            self._drop_rng = ops.dropout_rng(dev)
+
+    def _build_flat(self, dev, cap_elems, grad_pg):
+        """One flat fp32 gradient buffer, every .grad a 16-byte-aligned view into it (autograd
+        accumulates into the views in place); with a collective, its buckets of >= ``cap_elems``
+        elements and their all-reduce (GradReducer), told by hooks about the gradients autograd
+        accumulates."""
+        params, plan = self._params, self.plan
+        self._offs, n = flat_layout(params)
+        # zeros: the alignment padding between the views is never written by anything (the
+        # kernels and autograd write the views, _zero_grad writes zeros, a SUM all-reduce of
+        # zeros is zero), so it stays zero and the global norm may run over the whole buffer
+        self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
+        for p, off in zip(params, self._offs):
+            p.grad = self._flat[off:off + p.numel()].view_as(p)
+        if plan.collective != "none":
+            self.reducer = reducer = GradReducer(
+                self._flat, self._offs, cap_elems, mode=plan.collective, group=grad_pg,
+                comm_stream=plan.comm_stream, flagged=plan.flagged,
+                emulate=parse_emulate_rccl(os.environ.get("SAE_EMULATE_RCCL", "")))
+        if plan.hooks:
+            for i, p in enumerate(params):
+                p.register_post_accumulate_grad_hook(lambda _p, i=i: reducer.on_ready(i))
+
+    def _build_optimizer(self, lr, weight_decay, persistent_casts):
+        kw = dict(lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay)
+        if self.plan.fused:
+            # the bf16 Dense copies written by the update (models that name them, bf16 compute)
+            model = self.model
+            groups = model.cast_groups() if persistent_casts and hasattr(model, "cast_groups") else None
+            return FusedAdamW(self._params, self._flat, cast_groups=groups, clip_grad=self.clip_grad,
+                              lr_schedule=self.lr_schedule, **kw)
+        # the torch optimizer: clip and schedule in torch ops before its step (_opt_step)
+        self._count = 0
+        self._lr_now = self._grad_norm = None
+        if self.plan.capturable:
+            kw["capturable"] = True   # step counters on the device: replayable
+        try:
+            return torch.optim.AdamW(self._params, fused=True, **kw)
+        except (RuntimeError, TypeError):
+            return torch.optim.AdamW(self._params, foreach=True, **kw)
 
     @staticmethod
     def _broadcast_from_rank0(tensors):
@@ -557,83 +605,6 @@ class TrainStep:
                 for t in ts:
                     t.copy_(flat[off:off + t.numel()].view_as(t))
                     off += t.numel()
-
-    # ---- the overlapped bucket all-reduce
-    def _arm_overlap_hooks(self):
-        """A parameter's gradient is final when the kernel writing its sink has been enqueued
-        (_on_sink, the listener of this step's GradSinks) or, for gradients autograd accumulates, after its accumulation
-        (post-accumulate-grad hook); the bucket holding it is launched once all of its parameters
-        are final."""
-        self._armed = False
-        self._ptr_to_idx = {p.grad.data_ptr(): i for i, p in enumerate(self._params)}
-        for i, p in enumerate(self._params):
-            p.register_post_accumulate_grad_hook(lambda _p, i=i: self._on_ready(i))
-        if self._flat.is_cuda:
-            self._comm = torch.cuda.Stream(device=self._flat.device)
-
-    def _on_sink(self, ptr):
-        i = self._ptr_to_idx.get(ptr)
-        if i is not None:
-            self._on_ready(i)
-
-    def _on_ready(self, i):
-        if not self._armed or i in self._ready:
-            return
-        self._ready.add(i)
-        b = self._bucket_of[i]
-        self._remaining[b] -= 1
-        if self._remaining[b] == 0:
-            self._launch_bucket(b)
-
-    def _launch_bucket(self, b):
-        lo, hi = self._buckets[b]
-        t = self._flat[lo:hi]
-        self._launched[b] = True
-        if not self._comm_on:   # the capture's warm-up steps: no collective
-            return
-        if self._flagged and torch.cuda.is_current_stream_capturing():
-            # flagged graph: a mark on the captured chain; the collective is issued after the replay
-            ops.flag_bump(self._flags, b)
-            self._flag_order.append(b)
-            return
-        if t.is_cuda:
-            # the comm stream picks up everything enqueued so far on the compute stream (this
-            # bucket's gradient kernels included) and runs the RCCL all-reduce beside the rest of
-            # the backward; inside a graph capture this is a fork of the captured graph
-            self._comm.wait_stream(torch.cuda.current_stream(t.device))
-            self._allreduce_on_comm(t)
-        else:
-            self._works.append(dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=True))
-
-    def _allreduce_on_comm(self, t):
-        """The SUM all-reduce of bucket ``t`` on the communication stream, which the caller has made
-        wait for the bucket's gradients; under the RCCL emulation, the occupancy kernel behind it."""
-        with torch.cuda.stream(self._comm):
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self._cpg)
-            if self._emulate is not None:
-                ch, bw, wd, lds, thr = self._emulate
-                usec = 2.0 * (wd - 1) / wd * t.numel() * 4 / (bw * 1e3)
-                ops.occupy_cus(self._comm, ch, usec, threads=thr, lds_bytes=lds)
-
-    def _begin_overlap(self):
-        self._ready = set()
-        self._remaining = [len(ms) for ms in self._bucket_params]
-        self._launched = [False] * len(self._buckets)
-        self._works = []
-        self._armed = True
-
-    def _end_overlap(self):
-        self._armed = False
-        for b in range(len(self._buckets)):   # buckets holding a parameter that got no gradient
-            if not self._launched[b]:
-                self._launch_bucket(b)
-        if self._flat.is_cuda:
-            if not (self._flagged and torch.cuda.is_current_stream_capturing()):
-                torch.cuda.current_stream(self._flat.device).wait_stream(self._comm)   # the join
-        else:
-            for w in self._works:
-                w.wait()
-        self._works = []
 
     # ---- pieces of one step
     def _zero_grad(self):
@@ -666,59 +637,28 @@ class TrainStep:
             self._drop_rng.advance()
         self._zero_grad()
         sinks = self._sinks
-        overlap = self.collective == "overlap"
-        try:   # (the sink window: this step's forward + backward only)
-            with sinks.backward() if sinks is not None else contextlib.nullcontext():
-                if overlap:
-                    self._begin_overlap()
-                if self.input_layout == "NHWC":
-                    logits = self.model(images, is_training=True)
-                else:
-                    logits = self.model(images, is_training=True, layout=self.input_layout)
-                loss = smoothed_cross_entropy(logits, labels, self.smoothing)
-                # world > 1: the SUM all-reduce of the per-rank gradients of loss / world is the
-                # gradient of the global-batch mean (survey D9)
-                (loss / self.world if self.world > 1 else loss).backward()
-                if sinks is not None:
-                    sinks.join()   # every weight gradient written before the update
-                if overlap:
-                    self._end_overlap()
-        finally:
-            if overlap:
-                self._armed = False
+        # the sink window (this step's forward + backward only) and, inside it, the reducer's: its
+        # end launches what is left and joins the collectives, after every weight gradient is written
+        with sinks.backward() if sinks is not None else contextlib.nullcontext(), \
+                self.reducer.window() if self.collective == "overlap" else contextlib.nullcontext():
+            if self.input_layout == "NHWC":
+                logits = self.model(images, is_training=True)
+            else:
+                logits = self.model(images, is_training=True, layout=self.input_layout)
+            loss = smoothed_cross_entropy(logits, labels, self.smoothing)
+            # world > 1: the SUM all-reduce of the per-rank gradients of loss / world is the
+            # gradient of the global-batch mean (survey D9)
+            (loss / self.world if self.world > 1 else loss).backward()
+            if sinks is not None:
+                sinks.join()   # every weight gradient written before the update
         if sinks is not None and self.graph and not torch.cuda.is_current_stream_capturing():
             self._note_sunk()
         return loss.detach()
 
-    def _allreduce(self):
-        """The all-reduce between two graphs ("between" / "host"); "overlap" runs it inside the
-        backward and "none" has none."""
-        if self.collective in ("none", "overlap") or not self._comm_on:
-            return
-        if self.collective == "host":
-            # rehearsal of the multi-rank step on fewer GPUs (SAE_DIST_BACKEND=gloo): one explicit
-            # host round trip (gloo's own CUDA path stalled for seconds behind the graph replays)
-            host = self._flat.cpu()
-            dist.all_reduce(host, op=dist.ReduceOp.SUM)
-            self._flat.copy_(host)
-            return
-        # every bucket in flight at once on the process group's stream; the optimizer's graph
-        # replay waits for them on the compute stream (no host synchronisation)
-        works = [dist.all_reduce(self._flat[lo:hi], op=dist.ReduceOp.SUM, group=self._cpg, async_op=True)
-                 for lo, hi in self._buckets]
-        for w in works:
-            w.wait()
-
-    def _issue_flagged(self):
-        """After a replay of the flagged forward + backward graph: on the communication stream, each
-        bucket's wait for its flag (bumped by this replay) and its all-reduce, in the captured order;
-        the compute stream joins the communication stream before the optimizer's graph."""
-        self._epoch += 1
-        for b in self._flag_order:
-            lo, hi = self._buckets[b]
-            ops.stream_wait_flag(self._comm, self._flags, b, self._epoch)
-            self._allreduce_on_comm(self._flat[lo:hi])
-        torch.cuda.current_stream(self._flat.device).wait_stream(self._comm)
+    def _between(self, replayed: bool = False):
+        """The collectives between the forward + backward and the optimizer (GradReducer.between)."""
+        if self.reducer is not None:
+            self.reducer.between(replayed)
 
     def _opt_step(self):
         """The optimizer step.  FusedAdamW clips and schedules on the device; for torch.optim.AdamW
@@ -755,63 +695,64 @@ class TrainStep:
 
     def _eager(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         loss = self._fwd_bwd(images, labels)
-        self._allreduce()
+        self._between()
         self._opt_step()
         return loss
+
+    def _opt_snapshot(self):
+        """The optimizer's state: FusedAdamW's tensors, or torch.optim.AdamW's per-parameter dicts."""
+        if isinstance(self.opt, FusedAdamW):
+            return [t.clone() for t in self.opt.state_tensors()]
+        return {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.opt.state[p].items()}
+                for p in self._params if p in self.opt.state and self.opt.state[p]}
+
+    def _opt_restore(self, snap):
+        if isinstance(self.opt, FusedAdamW):
+            for t, v in zip(self.opt.state_tensors(), snap):
+                t.copy_(v)
+            self.opt.refresh_casts()   # the bf16 copies of the restored weights
+            return
+        for p in self._params:
+            old = snap.get(id(p))
+            for k, v in (self.opt.state.get(p) or {}).items():
+                if not torch.is_tensor(v):
+                    continue
+                if old is not None and torch.is_tensor(old.get(k)):
+                    v.copy_(old[k])
+                else:   # state created by the warm-up: a fresh optimizer's zeros
+                    v.zero_()
+
+    def _warm_up(self):
+        """Two eager steps on a side stream before the capture (allocator, library and optimizer
+        state) with the collectives off -- the gradient group stays free of eager work until its
+        collectives are captured (GradReducer) -- and then everything they changed put back, so that
+        the first call performs exactly ONE update (the reference's one update per batch,
+        train.py:94-100)."""
+        dev = self._images.device
+        snap = [p.detach().clone() for p in self._params]
+        snap_opt = self._opt_snapshot()
+        snap_rng = self._drop_rng.state.clone() if self._drop_rng is not None else None
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with self.reducer.paused() if self.reducer is not None else contextlib.nullcontext():
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self._eager(self._images, self._labels)
+        torch.cuda.current_stream(dev).wait_stream(s)
+        with torch.no_grad():
+            for p, v in zip(self._params, snap):
+                p.copy_(v)
+            if snap_rng is not None:   # the warm-up steps advanced the dropout offset
+                self._drop_rng.state.copy_(snap_rng)
+            self._opt_restore(snap_opt)
+        if not self.flat:
+            self.opt.zero_grad(set_to_none=True)
 
     def _capture(self, images: torch.Tensor, labels: torch.Tensor):
         self._images = images.clone()
         self._labels = labels.clone()
-        params = self._params
-        snap = [p.detach().clone() for p in params]
-        fused = isinstance(self.opt, FusedAdamW)
-        snap_fused = [t.clone() for t in self.opt.state_tensors()] if fused else None
-        had_state = set() if fused else {id(p) for p in params if p in self.opt.state and self.opt.state[p]}
-        snap_state = {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.opt.state[p].items()}
-                      for p in params if id(p) in had_state}
-        snap_rng = self._drop_rng.state.clone() if self._drop_rng is not None else None
-        s = torch.cuda.Stream(device=images.device)
-        s.wait_stream(torch.cuda.current_stream(images.device))
-        # warm-up on a side stream (allocator, library and optimizer state), collectives off: the
-        # gradient group stays free of eager work until its collectives are captured (above)
-        self._comm_on = False
-        try:
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._eager(self._images, self._labels)
-        finally:
-            self._comm_on = True
-        torch.cuda.current_stream(images.device).wait_stream(s)
-        # the warm-up steps were only for the allocator and the optimizer's lazily created state:
-        # put parameters and optimizer state back, so that the first call performs exactly ONE
-        # update (the reference's one update per batch, train.py:94-100)
-        with torch.no_grad():
-            for p, v in zip(params, snap):
-                p.copy_(v)
-            if snap_rng is not None:   # the warm-up steps advanced the dropout offset
-                self._drop_rng.state.copy_(snap_rng)
-            if fused:
-                for t, v in zip(self.opt.state_tensors(), snap_fused):
-                    t.copy_(v)
-                self.opt.refresh_casts()   # the bf16 copies of the restored weights
-            for p in ([] if fused else params):
-                st = self.opt.state.get(p)
-                if not st:
-                    continue
-                old = snap_state.get(id(p))
-                for k, v in st.items():
-                    if not torch.is_tensor(v):
-                        continue
-                    if old is not None and torch.is_tensor(old.get(k)):
-                        v.copy_(old[k])
-                    else:   # state created by the warm-up: a fresh optimizer's zeros
-                        v.zero_()
-        if not self.flat:
-            self.opt.zero_grad(set_to_none=True)
-        # thread_local: RCCL's watchdog thread keeps querying the events of the default group's
-        # eager work (the parameter broadcast) while the capture runs; a "global" capture would
-        # refuse those queries (hipErrorStreamCaptureUnsupported, fatal in the watchdog)
-        mode = "thread_local" if self.pg else "global"
+        self._warm_up()
+        mode = self.plan.capture_mode
         try:
             if not self.two_graphs:     # the whole step (with the overlapped collectives) in one graph
                 g = torch.cuda.CUDAGraph()
@@ -820,8 +761,8 @@ class TrainStep:
                 self._g = g
             else:                 # the collectives stay outside: two graphs around them
                 g, go = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                if self._flagged:
-                    self._flag_order = []
+                if self.reducer is not None:
+                    self.reducer.reset_flag_order()
                 with torch.cuda.graph(g, capture_error_mode=mode):
                     self._loss = self._fwd_bwd(self._images, self._labels)
                 with torch.cuda.graph(go, capture_error_mode=mode):
@@ -854,11 +795,11 @@ class TrainStep:
         if self._g is not None or self._g_opt is not None:
             torch.cuda.synchronize()
         self._g = self._g_opt = None
-        if dist.is_initialized():
-            for attr in ("_cpg", "_flag_pg"):
-                if getattr(self, attr) is not None:
-                    dist.destroy_process_group(getattr(self, attr))
-                    setattr(self, attr, None)
+        if self.reducer is not None:
+            self.reducer.close()
+        if self._flag_pg is not None and dist.is_initialized():
+            dist.destroy_process_group(self._flag_pg)
+            self._flag_pg = None
         if isinstance(self.opt, FusedAdamW):
             self.opt.close()
 
@@ -885,9 +826,6 @@ class TrainStep:
             self.opt.refresh_casts(only_if_stale=True)
         self._g.replay()
         if self._g_opt is not None:
-            if self._flagged:
-                self._issue_flagged()
-            else:
-                self._allreduce()
+            self._between(replayed=True)
             self._g_opt.replay()
         return self._loss

@@ -51,15 +51,15 @@ def _worker(rank, world, port, out):
     # order the backward completes the parameters), each at least the cap unless it is the last
     # every view 16-byte aligned (the in-place gradient kernels' vector stores; l2.bias has 5 elements)
     n = step._flat.numel()
-    b = step._buckets
+    b = step.reducer.buckets
     assert b[0][1] == n and b[-1][0] == 0 and all(b[i][0] == b[i + 1][1] for i in range(len(b) - 1))
     assert len(b) > 1 and all(p.grad.data_ptr() >= step._flat.data_ptr() for p in step.model.parameters())
     assert all(p.grad.data_ptr() % 16 == 0 for p in step.model.parameters())
     # the buckets' all-reduces are launched from inside the backward, as each bucket completes
     assert step.collective == "overlap"
     launched = []
-    orig = step._launch_bucket
-    step._launch_bucket = lambda bi: (launched.append((bi, len(step._ready))), orig(bi))[1]
+    orig = step.reducer.launch
+    step.reducer.launch = lambda bi: (launched.append((bi, len(step.reducer.ready))), orig(bi))[1]
     for _ in range(3):
         step(x[rank * per:(rank + 1) * per], y[rank * per:(rank + 1) * per])
     # bucket 0 (the last parameters) goes out before the backward has finished every gradient
@@ -157,14 +157,14 @@ def _alias_worker(rank, world, port, out):
     ti = [i for i, p in enumerate(step._params) if p is step.model.t][0]
     lo, hi = step._offs[ti], step._offs[ti] + step.model.t.numel()
     seen = []
-    orig = step._launch_bucket
+    orig = step.reducer.launch
 
     def spy(bi):
-        blo, bhi = step._buckets[bi]
+        blo, bhi = step.reducer.buckets[bi]
         if blo <= lo and hi <= bhi:   # the bucket holding the shared transform: its gradient as launched
             seen.append(step._flat[lo:hi].clone())
         return orig(bi)
-    step._launch_bucket = spy
+    step.reducer.launch = spy
     for _ in range(2):
         step(x[rank * per:(rank + 1) * per], y[rank * per:(rank + 1) * per])
         assert seen and torch.isfinite(seen[-1]).all()

@@ -39,25 +39,25 @@ def main(model):
     s_b = None
     try:
         s_b = train.TrainStep(m_b, global_batch=8, device=dev, graph=True, bucket_cap_mb=4.0)
-        assert s_b.collective == "overlap" and len(s_b._buckets) > 1
+        assert s_b.collective == "overlap" and len(s_b.reducer.buckets) > 1
         order = []
-        orig = s_b._launch_bucket
-        s_b._launch_bucket = lambda bi: (order.append((bi, len(s_b._ready))), orig(bi))[1]
+        orig = s_b.reducer.launch
+        s_b.reducer.launch = lambda bi: (order.append((bi, len(s_b.reducer.ready))), orig(bi))[1]
         g = torch.Generator(device=dev).manual_seed(3)
         data = [(torch.randn(8, 224, 224, 3, device=dev, generator=g),
                  torch.randint(0, 1000, (8,), device=dev, generator=g)) for _ in range(3)]
         la = [float(s_a(x, y)) for x, y in data]
         lb = [float(s_b(x, y)) for x, y in data]
-        nb = len(s_b._buckets)
+        nb = len(s_b.reducer.buckets)
         assert sorted(bi for bi, _ in order[-nb:]) == list(range(nb))     # the captured backward's launches
         assert order[-nb][1] < len(s_b._params)                            # the first before the last gradient
         if os.environ.get("SAE_FLAGGED", "1") != "0":
             # flagged: a linear forward + backward graph with one flag bump per bucket, the optimizer's
             # graph, and the all-reduces issued per replay behind the flags (one per bucket per replay)
             assert s_b._flagged and s_b._g is not None and s_b._g_opt is not None and s_b.graph
-            assert sorted(s_b._flag_order) == list(range(nb))
+            assert sorted(s_b.reducer.flag_order) == list(range(nb))
             torch.cuda.synchronize()
-            assert s_b._flags.tolist() == [len(data)] * nb, s_b._flags.tolist()
+            assert s_b.reducer.flags.tolist() == [len(data)] * nb, s_b.reducer.flags.tolist()
         else:
             assert s_b._g is not None and s_b._g_opt is None and s_b.graph   # one graph, collectives inside
         assert la == lb, (la, lb)

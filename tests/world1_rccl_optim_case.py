@@ -47,7 +47,7 @@ def main(model):
     s_b = None
     try:
         s_b = train.TrainStep(m_b, bucket_cap_mb=4.0, **kw)
-        assert s_b.collective == "overlap" and len(s_b._buckets) > 1
+        assert s_b.collective == "overlap" and len(s_b.reducer.buckets) > 1
         la, lb, ha, hb = [], [], [], []
         for x, y in data:
             la.append(float(s_a(x, y)))
@@ -56,7 +56,7 @@ def main(model):
             lb.append(float(s_b(x, y)))
             hb.append(s_b.opt.hyper.tolist())
         assert s_b._flagged and s_b._g is not None and s_b._g_opt is not None and s_b.graph
-        assert sorted(s_b._flag_order) == list(range(len(s_b._buckets)))
+        assert sorted(s_b.reducer.flag_order) == list(range(len(s_b.reducer.buckets)))
         assert la == lb, (la, lb)
         assert ha == hb, (ha, hb)                        # lr_t, clip_scale, grad_norm of every step
         assert all(abs(h[0] - want) <= 1e-9 for h, want in zip(hb, (0.0, 5e-4, 1e-3))), hb
