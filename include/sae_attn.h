@@ -562,6 +562,34 @@ int sae_smoothed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void*
                         int32_t dtype, const int64_t* labels, float alpha, const float* lse,
                         const float* grad_loss, void* dlogits, int64_t ldd);
 
+/* The same loss against mixup / cutmix targets (train.py:83-90 with the default augmentation:
+   rho onehot(labels) + (1 - rho) onehot(mix_labels), then optax.smooth_labels), with the top-k
+   ranks of utils.topk_correct (train.py:98-99) from the same pass:
+     row_loss_r = lse_r - (1 - alpha) (rho_r x[r, labels[r]] + (1 - rho_r) x[r, mix_labels[r]])
+                  - (alpha / classes) sum_c x[r, c]
+   mix_labels (int64 [rows]) and ratio (fp32 [rows], rho) are both NULL (one label per row) or both
+   set.  With them NULL, or with ratio == 1 and finite logits, lse, row_loss, *loss and dlogits are
+   bit-identical to sae_smoothed_ce_fwd / _bwd.  rank (int32 [rows]) and top (fp32 [2], device
+   memory) are both NULL (no metrics) or both set: rank[r] = the number of classes a stable
+   ascending argsort of row r places above labels[r] -- class c ranks above label y iff x[c] > x[y],
+   or x[c] is NaN and x[y] is not, or they compare equal (-0 == +0; both NaN) and c > y; a label
+   outside [0, classes) gets rank = classes -- and top[0], top[1] = the fractions of rows with
+   rank < 1 and rank < 5.  bwd writes dlogits = (*grad_loss / rows) (softmax(x_r)
+   - (1 - alpha) (rho [c == labels[r]] + (1 - rho) [c == mix_labels[r]]) - alpha / classes). */
+int sae_mixed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
+                     const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha, float* lse,
+                     float* row_loss, int32_t* rank, float* loss, float* top);
+int sae_mixed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
+                     const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha,
+                     const float* lse, const float* grad_loss, void* dlogits, int64_t ldd);
+
+/* Evaluation totals: adds one batch's row_loss / rank (as sae_mixed_ce_fwd wrote them) into the
+   SAE_CE_ACCUM_BYTES device accumulator acc = {double loss_sum; int64_t top1, top5, samples} (8-byte
+   aligned; the caller zeroes it).  The losses are added in double, in row order.  Stream-ordered, no
+   atomics: replays of a captured graph keep accumulating. */
+#define SAE_CE_ACCUM_BYTES 32
+int sae_ce_accumulate(void* stream, int32_t rows, const float* row_loss, const int32_t* rank, void* acc);
+
 /* Diagnostic: occupy `workgroups` workgroups of `threads` threads, each holding `lds_bytes` of LDS,
    for `usec` microseconds (a timed s_sleep loop, no memory traffic), on `stream`.  Used by
    bench.py --emulate-rccl to stand in, on one GPU, for the RCCL all-reduce kernels that share the

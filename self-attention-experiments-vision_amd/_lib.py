@@ -116,6 +116,9 @@ _PROTOS = [
     ("sae_tokens_bwd", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("sae_smoothed_ce_fwd", _i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp]),
     ("sae_smoothed_ce_bwd", _i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _i64]),
+    ("sae_mixed_ce_fwd", _i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    ("sae_mixed_ce_bwd", _i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64]),
+    ("sae_ce_accumulate", _i32, [_vp, _i32, _vp, _vp, _vp]),
     ("sae_occupy_cus", _i32, [_vp, _i32, _i32, _i32, _f32]),
     ("sae_flag_bump", _i32, [_vp, _vp, _i32]),
     ("sae_stream_wait_flag", _i32, [_vp, _vp, ctypes.c_uint32]),
@@ -158,6 +161,7 @@ SAE_ADAMW_CHUNK = 2048
 SAE_ADAMW_NORM_SPAN = 16384
 SAE_ADAMW_PREPARE_PASS = 256
 SAE_LR_CONSTANT, SAE_LR_WARMUP_COSINE = 0, 1
+SAE_CE_ACCUM_BYTES = 32   # {double loss_sum; int64 top1, top5, samples}
 
 
 class SaeError(RuntimeError):

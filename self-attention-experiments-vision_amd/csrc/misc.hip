@@ -1,6 +1,7 @@
 // misc.hip -- the rest of the C ABI: residual add + LayerNorm (ln.h), the encoder input tokens
 // (tokens.h), the hidden-state dropout of row-major activations (drop_rows.h: their dropout forms
-// and the standalone kernels), the smoothed cross-entropy (loss.h), AdamW (adamw.h), the stream
+// and the standalone kernels), the smoothed cross-entropy, its mixup / cutmix form with top-k and the
+// evaluation accumulator (loss.h), AdamW (adamw.h), the stream
 // utilities of bench.py, and the library's error string and version.
 #include "ln.h"
 #include "loss.h"
@@ -390,6 +391,58 @@ int sae_smoothed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void*
   return launch("smoothed_ce_bwd", smoothed_ce_bwd_kernel<float>, (long long)rows, dim3(256), 0, st,
                 reinterpret_cast<const float*>(logits), (long long)ld, labels, rows, classes, alpha, lse, grad_loss,
                 reinterpret_cast<float*>(dlogits), (long long)ldd);
+}
+
+// mix_labels / ratio both NULL (one label per row) or both set; rank / top both NULL (no metrics) or both set
+int sae_mixed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
+                     const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha, float* lse,
+                     float* row_loss, int32_t* rank, float* loss, float* top) {
+  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
+  if ((mix_labels == nullptr) != (ratio == nullptr))
+    return fail(SAE_EINVAL, "mixed_ce_fwd: mix_labels and ratio must both be given or both be NULL");
+  if ((rank == nullptr) != (top == nullptr))
+    return fail(SAE_EINVAL, "mixed_ce_fwd: rank and top must both be given or both be NULL");
+  if (!lse || !row_loss || !loss) return fail(SAE_EINVAL, "mixed_ce_fwd: NULL lse / row_loss / loss");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = dtype == SAE_DTYPE_BF16
+                     ? launch("mixed_ce_fwd", mixed_ce_fwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
+                              reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, mix_labels, ratio, classes,
+                              alpha, lse, row_loss, (int*)rank)
+                     : launch("mixed_ce_fwd", mixed_ce_fwd_kernel<float>, (long long)rows, dim3(256), 0, st,
+                              reinterpret_cast<const float*>(logits), (long long)ld, labels, mix_labels, ratio, classes,
+                              alpha, lse, row_loss, (int*)rank);
+  if (rc) return rc;
+  return launch("mixed_ce_mean", mixed_ce_mean_kernel, 1LL, dim3(256), 0, st, (const float*)row_loss,
+                (const int*)rank, rows, loss, top);
+}
+
+int sae_mixed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
+                     const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha,
+                     const float* lse, const float* grad_loss, void* dlogits, int64_t ldd) {
+  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
+  if ((mix_labels == nullptr) != (ratio == nullptr))
+    return fail(SAE_EINVAL, "mixed_ce_bwd: mix_labels and ratio must both be given or both be NULL");
+  if (!lse || !grad_loss || !dlogits || ldd < classes)
+    return fail(SAE_EINVAL, "mixed_ce_bwd: NULL lse / grad_loss / dlogits or ldd < classes");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SAE_DTYPE_BF16)
+    return launch("mixed_ce_bwd", mixed_ce_bwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
+                  reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, mix_labels, ratio, rows, classes, alpha,
+                  lse, grad_loss, reinterpret_cast<__bf16*>(dlogits), (long long)ldd);
+  return launch("mixed_ce_bwd", mixed_ce_bwd_kernel<float>, (long long)rows, dim3(256), 0, st,
+                reinterpret_cast<const float*>(logits), (long long)ld, labels, mix_labels, ratio, rows, classes, alpha,
+                lse, grad_loss, reinterpret_cast<float*>(dlogits), (long long)ldd);
+}
+
+static_assert(sizeof(CeAccum) == SAE_CE_ACCUM_BYTES, "the evaluation accumulator is 32 bytes");
+
+int sae_ce_accumulate(void* stream, int32_t rows, const float* row_loss, const int32_t* rank, void* acc) {
+  if (rows < 1 || rows > SAE_CE_MAX_ROWS)
+    return fail(SAE_EINVAL, "ce_accumulate: rows %d (1..%d)", rows, SAE_CE_MAX_ROWS);
+  if (!row_loss || !rank || !acc) return fail(SAE_EINVAL, "ce_accumulate: NULL row_loss / rank / acc");
+  if ((uintptr_t)acc & 7) return fail(SAE_EINVAL, "ce_accumulate: acc must be 8-byte aligned");
+  return launch("ce_accumulate", ce_accumulate_kernel, 1LL, dim3(256), 0, (hipStream_t)stream, row_loss,
+                (const int*)rank, rows, reinterpret_cast<CeAccum*>(acc));
 }
 
 // ---------------------------------------------------------------------------------- AdamW

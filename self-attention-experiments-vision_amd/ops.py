@@ -941,6 +941,14 @@ def refresh_persistent_casts(groups, only_if_stale: bool = False) -> None:
         _run_casts(entries)
 
 
+def persistent_cast_entries(groups) -> tuple:
+    """Per group, the persistent entry serving it (None: none does).  A captured forward reads the
+    copies it was captured with: its owner keeps this tuple (and with it the buffers) and captures
+    again when an entry is no longer the same object."""
+    ents = (_CASTS.get(_cast_key(ws)) for ws in groups)
+    return tuple(e if e is not None and e.owner is not None else None for e in ents)
+
+
 def _cast_lookup(ws):
     """(bf16 [K, N], bf16 [N, K]) of the group ``ws`` from the registry, or None."""
     e = _CASTS.get(_cast_key(ws))
@@ -1639,6 +1647,103 @@ def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, alpha: fl
     if logits.dim() != 2 or logits.stride(1) != 1:
         logits = logits.reshape(-1, logits.shape[-1]).contiguous()
     return _SmoothedCE.apply(logits, labels.to(torch.int64).contiguous(), alpha)
+
+
+class _MixedCE(torch.autograd.Function):
+    """The smoothed cross entropy against mixup / cutmix targets (train.py:83-90 with ``mix_labels`` /
+    ``ratio``) and, with ``metrics``, the top-1 / top-5 fractions of utils.topk_correct from the same
+    pass (sae_mixed_ce_fwd / _bwd).  Returns ``(loss, top, row_loss, rank)``: only the loss is
+    differentiable; ``top`` [2], ``row_loss`` [R] and ``rank`` [R] feed the metrics and the evaluation
+    accumulator (``top`` / ``rank`` empty without metrics)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, mix_labels, ratio, alpha, metrics):
+        lib = L.load()
+        R, K = logits.shape
+        dev = logits.device
+        lse = torch.empty(R, dtype=torch.float32, device=dev)
+        row_loss = torch.empty(R, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        rank = torch.empty(R if metrics else 0, dtype=torch.int32, device=dev)
+        top = torch.empty(2 if metrics else 0, dtype=torch.float32, device=dev)
+        L.check(lib.sae_mixed_ce_fwd(_stream(logits), R, K, _ptr(logits), logits.stride(0), dtype_code(logits.dtype),
+                                     _ptr(labels), _ptr(mix_labels), _ptr(ratio), float(alpha), _ptr(lse),
+                                     _ptr(row_loss), _ptr(rank) if metrics else None, _ptr(loss),
+                                     _ptr(top) if metrics else None))
+        ctx.save_for_backward(logits, labels, lse, *(() if mix_labels is None else (mix_labels, ratio)))
+        ctx.alpha = float(alpha)
+        ctx.mark_non_differentiable(top, row_loss, rank)
+        return loss, top, row_loss, rank
+
+    @staticmethod
+    @_sinking
+    def backward(ctx, gloss, *_unused):
+        lib = L.load()
+        logits, labels, lse, *mix = ctx.saved_tensors
+        mix_labels, ratio = mix if mix else (None, None)
+        R, K = logits.shape
+        g = gloss.float().contiguous()
+        dx = torch.empty((R, K), dtype=logits.dtype, device=logits.device)
+        L.check(lib.sae_mixed_ce_bwd(_stream(logits), R, K, _ptr(logits), logits.stride(0), dtype_code(logits.dtype),
+                                     _ptr(labels), _ptr(mix_labels), _ptr(ratio), ctx.alpha, _ptr(lse), _ptr(g),
+                                     _ptr(dx), dx.stride(0)))
+        return dx, None, None, None, None, None
+
+
+def mixed_cross_entropy_rows(logits, labels, mix_labels=None, ratio=None, alpha=0.1, metrics=True):
+    """``mixed_cross_entropy`` with its per-row results: ``(loss, top [2], row_loss [R], rank [R])``, what
+    the evaluation accumulator (``ce_accumulate``) and ``train.topk_correct`` read."""
+    _require_gpu(logits, labels, mix_labels, ratio)
+    if (mix_labels is None) != (ratio is None):
+        raise ValueError("mixed_cross_entropy: mix_labels and ratio go together (both or neither)")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        logits = logits.reshape(-1, logits.shape[-1]).contiguous()
+    R = logits.shape[0]
+    labels = labels.to(torch.int64).contiguous()
+    if mix_labels is not None:
+        mix_labels = mix_labels.to(torch.int64).contiguous()
+        ratio = ratio.to(torch.float32).contiguous()
+        if mix_labels.numel() != R or ratio.numel() != R:
+            raise ValueError(f"mixed_cross_entropy: mix_labels / ratio need one entry per row ({R})")
+    if labels.numel() != R:
+        raise ValueError(f"mixed_cross_entropy: labels need one entry per row ({R})")
+    return _MixedCE.apply(logits, labels, mix_labels, ratio, alpha, bool(metrics))
+
+
+def mixed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, mix_labels: Optional[torch.Tensor] = None,
+                        ratio: Optional[torch.Tensor] = None, alpha: float = 0.1, metrics: bool = False):
+    """The smoothed cross entropy of [R, K] GPU logits (bf16 or fp32) against the targets
+    ``ratio onehot(labels) + (1 - ratio) onehot(mix_labels)`` (``mix_labels`` int [R], ``ratio`` float
+    [R]; both None: one label per row, bit-identical to ``smoothed_cross_entropy``).  ``metrics=True``
+    returns ``(loss, top1, top5)``: the fractions of rows whose first label is among the 1 / 5 largest
+    logits in stable-argsort order (0-d device tensors, not differentiable)."""
+    loss, top, _, _ = mixed_cross_entropy_rows(logits, labels, mix_labels, ratio, alpha, metrics)
+    return (loss, top[0], top[1]) if metrics else loss
+
+
+def ce_accumulate(row_loss: torch.Tensor, rank: torch.Tensor, acc: torch.Tensor) -> None:
+    """Add one batch's ``row_loss`` (fp32 [R]) and ``rank`` (int32 [R]) into the evaluation accumulator
+    ``acc`` (4 x int64 on the GPU holding {double loss_sum; int64 top1, top5, samples}:
+    ``sae_ce_accumulate``), on the current stream."""
+    _require_gpu(row_loss, rank, acc)
+    if (acc.dtype != torch.int64 or acc.numel() * 8 != L.SAE_CE_ACCUM_BYTES or not acc.is_contiguous()
+            or row_loss.dtype != torch.float32 or rank.dtype != torch.int32 or rank.numel() != row_loss.numel()
+            or not row_loss.is_contiguous() or not rank.is_contiguous()):
+        raise ValueError("ce_accumulate: row_loss fp32 [R], rank int32 [R], acc int64 [4], all contiguous")
+    L.check(L.load().sae_ce_accumulate(_stream(row_loss), row_loss.numel(), _ptr(row_loss), _ptr(rank), _ptr(acc)))
+
+
+def ce_accumulator_fields(acc: torch.Tensor):
+    """The two fields of an evaluation accumulator (int64 [4] holding {double loss_sum; int64 top1,
+    top5, samples}) as views of it: ``(loss_sum float64 [1], counts int64 [3])``.  The one place
+    that knows the layout on the Python side."""
+    return acc[:1].view(torch.float64), acc[1:]
+
+
+def read_ce_accumulator(acc: torch.Tensor):
+    """``(loss_sum, top1, top5, samples)`` of an evaluation accumulator, on the host (one sync)."""
+    loss_sum, counts = ce_accumulator_fields(acc.cpu())
+    return (float(loss_sum[0]), *(int(c) for c in counts))
 
 
 # ------------------------------------------------------------------------ encoder input tokens

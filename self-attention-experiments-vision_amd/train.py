@@ -28,7 +28,11 @@ the collective mode, one graph or two, flag-gated or not, which process groups, 
 and sinks exist.  ``TrainStep.__init__`` builds what the plan names.  The buckets and their
 all-reduce are a ``reducer.GradReducer`` (``TrainStep.reducer``, None without a process group).
 
-Loss: one-hot -> optax.smooth_labels(0.1) -> softmax cross-entropy, mean (train.py:83-92).
+Loss: one-hot -> optax.smooth_labels(0.1) -> softmax cross-entropy, mean (train.py:83-92); with
+``mix=True`` the one-hot is the default augmentation's mixup / cutmix target ``ratio onehot(labels) +
+(1 - ratio) onehot(mix_labels)`` and ``metrics=True`` adds utils.topk_correct of the step's logits
+(``step.top1`` / ``step.top5``), both from one HIP loss (ops.mixed_cross_entropy).  ``EvalStep`` is the
+reference's eval_step (train.py:112-120) with a device accumulator.
 Optimizer: the reference's chain (train.py:22-27,214-220): clip_by_global_norm(``clip_grad``),
 Adam, decoupled weight decay 1e-4, scale by the schedule.  ``lr_schedule=None`` keeps the constant
 rate 5e-4 * batch/512 and ``clip_grad=None`` no clip (the defaults, which launch exactly what a step
@@ -55,8 +59,9 @@ from . import ops
 from .reducer import GradReducer, parse_emulate_rccl
 from .sinks import GradSinks
 
-__all__ = ["smoothed_cross_entropy", "TrainStep", "init_distributed", "FusedAdamW", "WarmupCosine",
-           "reference_schedule", "StepFacts", "StepPlan", "step_facts", "step_facts_of_values", "step_plan"]
+__all__ = ["smoothed_cross_entropy", "mixed_cross_entropy", "topk_correct", "label_ranks", "TrainStep", "EvalStep",
+           "init_distributed", "FusedAdamW", "WarmupCosine", "reference_schedule", "StepFacts", "StepPlan",
+           "step_facts", "step_facts_of_values", "step_plan"]
 
 
 @dataclass(frozen=True)
@@ -108,6 +113,64 @@ def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, smoothing
     if logits.is_cuda:
         return ops.smoothed_cross_entropy(logits, labels, smoothing)
     return F.cross_entropy(logits.float(), labels, label_smoothing=smoothing)
+
+
+def label_ranks(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """Per row, the number of classes a stable ascending argsort of the row (jnp.argsort of
+    utils.topk_correct) places above the row's label: class c is above label y iff x[c] > x[y], or
+    x[c] is NaN and x[y] is not, or they compare equal (-0 == +0; both NaN) and c > y.  A label
+    outside [0, K) ranks K.  GPU logits: the rank the loss kernel counts (sae_mixed_ce_fwd); CPU
+    tensors: the same rule in torch ops.  int32 [R]."""
+    logits = logits.reshape(-1, logits.shape[-1])
+    if logits.is_cuda:
+        return ops.mixed_cross_entropy_rows(logits.detach(), labels, None, None, 0.0, True)[3]
+    x = logits.detach().float()
+    K = x.shape[1]
+    y = labels.reshape(-1).to(torch.int64)
+    ok = (y >= 0) & (y < K)
+    yc = y.clamp(0, K - 1)[:, None]
+    xy = x.gather(1, yc)
+    nx, ny = x.isnan(), xy.isnan()
+    cls = torch.arange(K)[None, :]
+    above = ((x > xy) | (nx & ~ny) | (((x == xy) | (nx & ny)) & (cls > yc))).sum(1)
+    return torch.where(ok, above, torch.full_like(above, K)).to(torch.int32)
+
+
+def topk_correct(logits: torch.Tensor, labels: torch.Tensor, topk=(1, 5)):
+    """utils.topk_correct (train.py:98-99): per k of ``topk`` a float32 [R] tensor, 1 where the row's
+    label is among the last k classes of the row's stable ascending argsort (ties go to the higher
+    class index, NaN sorts last), else 0."""
+    rank = label_ranks(logits, labels)
+    return tuple((rank < int(k)).float() for k in topk)
+
+
+def mixed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, mix_labels: Optional[torch.Tensor] = None,
+                        ratio: Optional[torch.Tensor] = None, smoothing: float = 0.1, metrics: bool = False):
+    """train.py:83-90 with the default augmentation's mixup / cutmix targets: ``ratio onehot(labels) +
+    (1 - ratio) onehot(mix_labels)``, optax.smooth_labels, mean softmax cross entropy.  ``mix_labels``
+    and ``ratio`` go together; both None is the one-label loss.  ``metrics=True`` returns ``(loss, top1,
+    top5)`` with the mean of ``topk_correct`` on the first label (train.py:98-99).  GPU logits take the
+    HIP loss (ops.mixed_cross_entropy); CPU tensors (the multi-process gloo tests' small models) take
+    torch's cross entropy with probability targets, which computes the same quantity.  The HIP loss
+    gives a label outside [0, K) no target term; the CPU branch refuses one (ValueError)."""
+    if logits.is_cuda:
+        return ops.mixed_cross_entropy(logits, labels, mix_labels, ratio, smoothing, metrics)
+    if (mix_labels is None) != (ratio is None):
+        raise ValueError("mixed_cross_entropy: mix_labels and ratio go together (both or neither)")
+    x = logits.float()
+    K = x.shape[-1]
+    for name, y in (("labels", labels), ("mix_labels", mix_labels)):
+        if y is not None and bool(((y < 0) | (y >= K)).any()):
+            raise ValueError(f"mixed_cross_entropy (CPU): {name} outside [0, {K})")
+    target = F.one_hot(labels.to(torch.int64), K).to(x.dtype)
+    if mix_labels is not None:
+        rho = ratio.to(x.dtype)[:, None]
+        target = rho * target + (1.0 - rho) * F.one_hot(mix_labels.to(torch.int64), K).to(x.dtype)
+    loss = F.cross_entropy(x, target, label_smoothing=smoothing)
+    if not metrics:
+        return loss
+    top1, top5 = topk_correct(logits, labels)
+    return loss, top1.mean(), top5.mean()
 
 
 def init_distributed():
@@ -483,17 +546,28 @@ class TrainStep:
     norm is part of the optimizer step, which every mode runs behind its join with the collectives.
     With the one-launch FusedAdamW both live on the device (graph-replayable); with
     ``torch.optim.AdamW`` (CPU or non-fp32 parameters) the same semantics run eagerly in torch ops
-    and ``graph=True`` is refused.  ``lr_now`` / ``grad_norm``: the last update's rate and norm."""
+    and ``graph=True`` is refused.  ``lr_now`` / ``grad_norm``: the last update's rate and norm.
+
+    ``mix=True``: ``step(images, labels, mix_labels, ratio)``, both extra arguments on every call (the
+    captured step copies them into static buffers, ``mix_buffers()``); with ``mix=False`` they are
+    refused.  ``metrics=True``: ``top1`` / ``top5``, the fractions of the last step's rank-local batch
+    whose first label is among the 1 / 5 largest logits (0-d device tensors, no sync)."""
 
     def __init__(self, model: torch.nn.Module, global_batch: int, lr: float = 5e-4, weight_decay: float = 1e-4,
                  label_smoothing: float = 0.1, bucket_cap_mb: float = 25.0, device: Optional[torch.device] = None,
                  graph: bool = False, input_layout: str = "NHWC", flat_grads: Optional[bool] = None,
                  grad_sinks: bool = True, two_graphs: Optional[bool] = None, persistent_casts: bool = True,
                  wgrad_stream: Optional[bool] = None, clip_grad: Optional[float] = None,
-                 lr_schedule: Optional[WarmupCosine] = None):
+                 lr_schedule: Optional[WarmupCosine] = None, mix: bool = False, metrics: bool = False):
         self.clip_grad = _check_clip(clip_grad)
         if lr_schedule is not None and not isinstance(lr_schedule, WarmupCosine):
             raise TypeError("TrainStep: lr_schedule must be a WarmupCosine or None")
+        # mix: every call carries the batch's mixup / cutmix partner labels and ratios; metrics: the
+        # loss kernel also ranks the labels (top1 / top5).  Neither is part of the step's structure
+        # (step_plan); with both off the step launches exactly what it launched without them.
+        self.mix, self.metrics = bool(mix), bool(metrics)
+        self._top1 = self._top5 = None
+        self._mix_labels = self._ratio = None
         self.lr_schedule = lr_schedule
         # input_layout "HWCN": the batch arrives as the reference's train-step feed [H, W, C, N]
         # (train.py:80, input_pipeline.py:187-191) and the model's patch GEMM gathers from it
@@ -632,7 +706,7 @@ class TrainStep:
         # many scattered ranges would cost more launches than the one full fill saves
         self._zero_ranges = ranges if len(ranges) <= 8 else None
 
-    def _fwd_bwd(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def _fwd_bwd(self, images: torch.Tensor, labels: torch.Tensor, mix_labels=None, ratio=None) -> torch.Tensor:
         if self._drop_rng is not None:
             self._drop_rng.advance()
         self._zero_grad()
@@ -645,7 +719,12 @@ class TrainStep:
                 logits = self.model(images, is_training=True)
             else:
                 logits = self.model(images, is_training=True, layout=self.input_layout)
-            loss = smoothed_cross_entropy(logits, labels, self.smoothing)
+            if self.mix or self.metrics:
+                loss = mixed_cross_entropy(logits, labels, mix_labels, ratio, self.smoothing, self.metrics)
+                if self.metrics:
+                    loss, self._top1, self._top5 = loss
+            else:
+                loss = smoothed_cross_entropy(logits, labels, self.smoothing)
             # world > 1: the SUM all-reduce of the per-rank gradients of loss / world is the
             # gradient of the global-batch mean (survey D9)
             (loss / self.world if self.world > 1 else loss).backward()
@@ -693,8 +772,19 @@ class TrainStep:
         clip_grad."""
         return self.opt.grad_norm if isinstance(self.opt, FusedAdamW) else self._grad_norm
 
-    def _eager(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        loss = self._fwd_bwd(images, labels)
+    @property
+    def top1(self):
+        """The fraction of the last step's rank-local batch whose label had the largest logit (stable
+        argsort order, utils.topk_correct): a 0-d device tensor, no sync; None without ``metrics``."""
+        return self._top1
+
+    @property
+    def top5(self):
+        """... whose label was among the five largest logits."""
+        return self._top5
+
+    def _eager(self, images: torch.Tensor, labels: torch.Tensor, mix_labels=None, ratio=None) -> torch.Tensor:
+        loss = self._fwd_bwd(images, labels, mix_labels, ratio)
         self._between()
         self._opt_step()
         return loss
@@ -737,7 +827,7 @@ class TrainStep:
         with self.reducer.paused() if self.reducer is not None else contextlib.nullcontext():
             with torch.cuda.stream(s):
                 for _ in range(2):
-                    self._eager(self._images, self._labels)
+                    self._eager(self._images, self._labels, self._mix_labels, self._ratio)
         torch.cuda.current_stream(dev).wait_stream(s)
         with torch.no_grad():
             for p, v in zip(self._params, snap):
@@ -748,23 +838,26 @@ class TrainStep:
         if not self.flat:
             self.opt.zero_grad(set_to_none=True)
 
-    def _capture(self, images: torch.Tensor, labels: torch.Tensor):
+    def _capture(self, images: torch.Tensor, labels: torch.Tensor, mix_labels=None, ratio=None):
         self._images = images.clone()
         self._labels = labels.clone()
+        if self.mix:
+            self._mix_labels = mix_labels.clone()
+            self._ratio = ratio.to(torch.float32).clone()
         self._warm_up()
         mode = self.plan.capture_mode
         try:
             if not self.two_graphs:     # the whole step (with the overlapped collectives) in one graph
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode=mode):
-                    self._loss = self._eager(self._images, self._labels)
+                    self._loss = self._eager(self._images, self._labels, self._mix_labels, self._ratio)
                 self._g = g
             else:                 # the collectives stay outside: two graphs around them
                 g, go = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 if self.reducer is not None:
                     self.reducer.reset_flag_order()
                 with torch.cuda.graph(g, capture_error_mode=mode):
-                    self._loss = self._fwd_bwd(self._images, self._labels)
+                    self._loss = self._fwd_bwd(self._images, self._labels, self._mix_labels, self._ratio)
                 with torch.cuda.graph(go, capture_error_mode=mode):
                     self._opt_step()
                 self._g, self._g_opt = g, go
@@ -811,17 +904,34 @@ class TrainStep:
             return None
         return self._images, self._labels
 
-    def __call__(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def mix_buffers(self):
+        """(mix_labels, ratio): the captured graph's static buffers of a ``mix=True`` step, once the
+        first call has captured it (None otherwise), for a loader to write into like ``input_buffers``."""
+        if self._g is None or not self.mix:
+            return None
+        return self._mix_labels, self._ratio
+
+    def __call__(self, images: torch.Tensor, labels: torch.Tensor, mix_labels: Optional[torch.Tensor] = None,
+                 ratio: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.mix and (mix_labels is None or ratio is None):
+            raise ValueError("TrainStep(mix=True): every call needs mix_labels and ratio")
+        if not self.mix and (mix_labels is not None or ratio is not None):
+            raise ValueError("TrainStep: mix_labels / ratio need mix=True")
         if not self.graph:
-            return self._eager(images, labels)
+            return self._eager(images, labels, mix_labels, ratio)
         if self._g is None:
-            self._capture(images, labels)
+            self._capture(images, labels, mix_labels, ratio)
             if not self.graph:
-                return self._eager(images, labels)
+                return self._eager(images, labels, mix_labels, ratio)
         if images.data_ptr() != self._images.data_ptr():
             self._images.copy_(images)
         if labels.data_ptr() != self._labels.data_ptr():
             self._labels.copy_(labels)
+        if self.mix:
+            if mix_labels.data_ptr() != self._mix_labels.data_ptr():
+                self._mix_labels.copy_(mix_labels)
+            if ratio.data_ptr() != self._ratio.data_ptr():
+                self._ratio.copy_(ratio)
         if isinstance(self.opt, FusedAdamW):
             self.opt.refresh_casts(only_if_stale=True)
         self._g.replay()
@@ -829,3 +939,125 @@ class TrainStep:
             self._between(replayed=True)
             self._g_opt.replay()
         return self._loss
+
+
+class EvalStep:
+    """``step(images, labels)`` = the reference's eval_step (train.py:112-120): a forward with
+    ``is_training=False`` under ``torch.no_grad()`` and the plain one-hot cross entropy (the mixed loss
+    with alpha = 0 and no partner labels), with the top-1 / top-5 ranks from the same kernel, added
+    into a device accumulator {double loss_sum; int64 top1, top5, samples} (``sae_ce_accumulate``).
+    Returns the batch's mean loss as a 0-d device tensor; no host sync.  It never advances the dropout
+    state and never touches ``.grad``.
+
+    graph=True (GPU): captured once and replayed with static ``images`` / ``labels``.  The graph reads
+    the bf16 Dense copies a ``FusedAdamW`` keeps current (refreshed before a replay if a weight was
+    changed in place outside the update); when no optimizer owns them it holds the casts from the
+    current fp32 weights itself.  When the copies change hands (an optimizer is built or closed) the
+    next call captures again.
+
+    ``result()`` is the one sync: the accumulator, summed over the default process group when there is
+    one, as per-sample means ``{"loss", "top_1_acc", "top_5_acc", "samples"}``.  (The reference sums
+    per-batch mean losses and divides by the sample count, train.py:240-250; see DESIGN.)  ``reset()``
+    zeroes the accumulator.  CPU tensors run the same steps in torch ops."""
+
+    def __init__(self, model: torch.nn.Module, device: Optional[torch.device] = None, graph: bool = False,
+                 input_layout: str = "NHWC"):
+        self.model, self.input_layout = model, input_layout
+        dev = torch.device(device) if device is not None else next(model.parameters()).device
+        self.device = dev
+        self.graph = bool(graph) and dev.type == "cuda" and torch.cuda.is_available()
+        # {double loss_sum; int64 top1, top5, samples} (ops.ce_accumulator_fields)
+        self._acc = torch.zeros(L.SAE_CE_ACCUM_BYTES // 8, dtype=torch.int64, device=dev)
+        self._g = self._images = self._labels = self._loss = None
+        self._cast_entries = ()
+
+    def _groups(self):
+        groups = self.model.cast_groups() if hasattr(self.model, "cast_groups") else None
+        return groups or []
+
+    def _step(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        with torch.no_grad():
+            if self.input_layout == "NHWC":
+                logits = self.model(images, is_training=False)
+            else:
+                logits = self.model(images, is_training=False, layout=self.input_layout)
+            if logits.is_cuda:
+                loss, _, row_loss, rank = ops.mixed_cross_entropy_rows(logits, labels, None, None, 0.0, True)
+                ops.ce_accumulate(row_loss, rank, self._acc)
+                return loss
+            row_loss = F.cross_entropy(logits.float(), labels.to(torch.int64), reduction="none")
+            rank = label_ranks(logits, labels)
+            loss_sum, counts = ops.ce_accumulator_fields(self._acc)
+            loss_sum += row_loss.double().sum()
+            counts += torch.stack([(rank < 1).sum(), (rank < 5).sum(), torch.tensor(rank.numel())])
+            return row_loss.mean()
+
+    def _capture(self, images: torch.Tensor, labels: torch.Tensor):
+        dev = self.device
+        self._images, self._labels = images.clone(), labels.clone()
+        # one eager step on a side stream (allocator, library state), its accumulation taken back
+        snap = self._acc.clone()
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            self._step(self._images, self._labels)
+        torch.cuda.current_stream(dev).wait_stream(s)
+        self._acc.copy_(snap)
+        self._cast_entries = ops.persistent_cast_entries(self._groups())
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local" if dist.is_initialized() else "global"):
+                self._loss = self._step(self._images, self._labels)
+            self._g = g
+        except RuntimeError as e:   # an op that cannot be captured: stay eager, say so once
+            import sys
+            print(f"[eval] HIP-graph capture failed ({e}); running the eager step", file=sys.stderr)
+            self.graph, self._g = False, None
+            torch.cuda.synchronize()
+
+    def __call__(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        if not self.graph:
+            return self._step(images, labels)
+        groups = self._groups()
+        now = ops.persistent_cast_entries(groups)
+        if self._g is not None and (len(now) != len(self._cast_entries)
+                                    or any(a is not b for a, b in zip(now, self._cast_entries))):
+            torch.cuda.synchronize()
+            self._g = None   # the copies the graph reads changed hands: capture again
+        if self._g is None:
+            self._capture(images, labels)
+            if not self.graph:
+                return self._step(images, labels)
+        if images.data_ptr() != self._images.data_ptr():
+            self._images.copy_(images)
+        if labels.data_ptr() != self._labels.data_ptr():
+            self._labels.copy_(labels)
+        ops.refresh_persistent_casts(groups, only_if_stale=True)
+        self._g.replay()
+        return self._loss
+
+    def input_buffers(self):
+        """(images, labels): the captured graph's static input buffers (None before the capture)."""
+        return None if self._g is None else (self._images, self._labels)
+
+    def reset(self):
+        self._acc.zero_()
+
+    def result(self) -> dict:
+        """The totals since the last ``reset()`` over every rank, as per-sample means (one host sync; the
+        SUM all-reduce goes through the host for gloo)."""
+        total = self._acc.clone()
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            if total.is_cuda and dist.get_backend() == "gloo":
+                total = total.cpu()
+            for field in ops.ce_accumulator_fields(total):   # a double and three integers: one SUM each
+                dist.all_reduce(field)
+        loss_sum, top1, top5, n = ops.read_ce_accumulator(total)
+        d = max(n, 1)
+        return {"loss": loss_sum / d, "top_1_acc": top1 / d, "top_5_acc": top5 / d, "samples": n}
+
+    def close(self):
+        """Release the captured graph."""
+        if self._g is not None:
+            torch.cuda.synchronize()
+        self._g = None

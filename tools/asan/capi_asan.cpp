@@ -210,6 +210,69 @@ static void validation() {
   expect(sae_smoothed_ce_fwd(nullptr, 0, 1000, q, 1000, SAE_DTYPE_BF16, static_cast<const int64_t*>(fake()), 0.1f,
                              fa, fa, fa) != SAE_OK,
          "ce zero rows");
+  // the mixed loss, its backward and the evaluation accumulator: every refusal on the host
+  {
+    const int64_t* lab = static_cast<const int64_t*>(fake());
+    const int64_t* mix = static_cast<const int64_t*>(fake());
+    int32_t* rank = static_cast<int32_t*>(fake());
+    expect(sae_mixed_ce_fwd(nullptr, 0, 1000, q, 1000, SAE_DTYPE_BF16, lab, nullptr, nullptr, 0.1f, fa, fa, nullptr,
+                            fa, nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd zero rows");
+    expect(sae_mixed_ce_fwd(nullptr, SAE_CE_MAX_ROWS + 1, 1000, q, 1000, SAE_DTYPE_BF16, lab, nullptr, nullptr, 0.1f,
+                            fa, fa, nullptr, fa, nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd too many rows");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 999, SAE_DTYPE_BF16, lab, nullptr, nullptr, 0.1f, fa, fa, nullptr, fa,
+                            nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd ld < classes");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, 9, lab, nullptr, nullptr, 0.1f, fa, fa, nullptr, fa, nullptr) ==
+               SAE_EINVAL,
+           "mixed_ce_fwd bad dtype");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, nullptr, 1000, SAE_DTYPE_BF16, lab, nullptr, nullptr, 0.1f, fa, fa,
+                            nullptr, fa, nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd null logits");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, nullptr, nullptr, nullptr, 0.1f, fa, fa,
+                            nullptr, fa, nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd null labels");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, nullptr, fa, 0.1f, fa, fa, nullptr, fa,
+                            nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd ratio without mix_labels");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, nullptr, 0.1f, fa, fa, nullptr, fa,
+                            nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd mix_labels without ratio");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, fa, 0.1f, fa, fa, rank, fa, nullptr) ==
+               SAE_EINVAL,
+           "mixed_ce_fwd rank without top");
+    expect(sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, fa, 0.1f, fa, fa, nullptr, nullptr,
+                            nullptr) == SAE_EINVAL,
+           "mixed_ce_fwd null loss");
+    int rc3 = sae_mixed_ce_fwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, fa, 0.1f, fa, fa, rank, fa, fa);
+    expect(rc3 == SAE_OK || rc3 == SAE_EHIP, "mixed_ce_fwd: valid launch without a GPU");
+    expect(sae_mixed_ce_bwd(nullptr, 0, 1000, q, 1000, SAE_DTYPE_BF16, lab, nullptr, nullptr, 0.1f, fa, fa, o, 1000) ==
+               SAE_EINVAL,
+           "mixed_ce_bwd zero rows");
+    expect(sae_mixed_ce_bwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, nullptr, fa, 0.1f, fa, fa, o, 1000) ==
+               SAE_EINVAL,
+           "mixed_ce_bwd ratio without mix_labels");
+    expect(sae_mixed_ce_bwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, fa, 0.1f, fa, fa, o, 999) ==
+               SAE_EINVAL,
+           "mixed_ce_bwd ldd < classes");
+    expect(sae_mixed_ce_bwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, fa, 0.1f, nullptr, fa, o, 1000) ==
+               SAE_EINVAL,
+           "mixed_ce_bwd null lse");
+    expect(sae_mixed_ce_bwd(nullptr, 8, 1000, q, 1000, SAE_DTYPE_BF16, lab, mix, fa, 0.1f, fa, fa, nullptr, 1000) ==
+               SAE_EINVAL,
+           "mixed_ce_bwd null dlogits");
+    void* acc = fake(SAE_CE_ACCUM_BYTES);
+    expect(sae_ce_accumulate(nullptr, 0, fa, rank, acc) == SAE_EINVAL, "ce_accumulate zero rows");
+    expect(sae_ce_accumulate(nullptr, SAE_CE_MAX_ROWS + 1, fa, rank, acc) == SAE_EINVAL, "ce_accumulate too many rows");
+    expect(sae_ce_accumulate(nullptr, 8, nullptr, rank, acc) == SAE_EINVAL, "ce_accumulate null row_loss");
+    expect(sae_ce_accumulate(nullptr, 8, fa, nullptr, acc) == SAE_EINVAL, "ce_accumulate null rank");
+    expect(sae_ce_accumulate(nullptr, 8, fa, rank, nullptr) == SAE_EINVAL, "ce_accumulate null acc");
+    expect(sae_ce_accumulate(nullptr, 8, fa, rank, static_cast<char*>(acc) + 4) == SAE_EINVAL,
+           "ce_accumulate misaligned acc");
+    rc3 = sae_ce_accumulate(nullptr, 8, fa, rank, acc);
+    expect(rc3 == SAE_OK || rc3 == SAE_EHIP, "ce_accumulate: valid launch without a GPU");
+  }
   // clip + schedule around AdamW: every refusal on the host, the schedule read from the caller's struct only
   {
     int32_t* step = static_cast<int32_t*>(fake());
