@@ -568,8 +568,9 @@ int sae_smoothed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void*
      row_loss_r = lse_r - (1 - alpha) (rho_r x[r, labels[r]] + (1 - rho_r) x[r, mix_labels[r]])
                   - (alpha / classes) sum_c x[r, c]
    mix_labels (int64 [rows]) and ratio (fp32 [rows], rho) are both NULL (one label per row) or both
-   set.  With them NULL, or with ratio == 1 and finite logits, lse, row_loss, *loss and dlogits are
-   bit-identical to sae_smoothed_ce_fwd / _bwd.  rank (int32 [rows]) and top (fp32 [2], device
+   set.  sae_smoothed_ce_fwd / _bwd is this pair with mix_labels, ratio, rank and top NULL (one host
+   path, one kernel family); ratio == 1 with finite logits gives the same bits of lse, row_loss,
+   *loss and dlogits as NULL does.  rank (int32 [rows]) and top (fp32 [2], device
    memory) are both NULL (no metrics) or both set: rank[r] = the number of classes a stable
    ascending argsort of row r places above labels[r] -- class c ranks above label y iff x[c] > x[y],
    or x[c] is NaN and x[y] is not, or they compare equal (-0 == +0; both NaN) and c > y; a label

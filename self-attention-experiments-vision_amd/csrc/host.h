@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "../../include/sae_attn.h"
 
@@ -65,6 +66,13 @@ int launch(const char* name, void (*kernel)(P...), long long grid, dim3 block, s
            A&&... args) {
   if (grid > 0x7fffffffLL) return fail(SAE_EUNSUPPORTED, "grid too large");
   return launch(name, kernel, dim3((unsigned)grid), block, lds, st, args...);
+}
+
+// A kernel template over the element type: fn(T*) (a null pointer that only carries the type) with
+// T = __bf16 or float by dtype, which the caller has checked to be one of the two.
+template <typename F>
+int by_dtype(int dtype, F&& fn) {
+  return dtype == SAE_DTYPE_BF16 ? fn(static_cast<__bf16*>(nullptr)) : fn(static_cast<float*>(nullptr));
 }
 
 // Development A/B knobs, read from the environment only in the dev build (build.py --dev defines

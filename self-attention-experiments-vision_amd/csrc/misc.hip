@@ -1,7 +1,7 @@
 // misc.hip -- the rest of the C ABI: residual add + LayerNorm (ln.h), the encoder input tokens
 // (tokens.h), the hidden-state dropout of row-major activations (drop_rows.h: their dropout forms
-// and the standalone kernels), the smoothed cross-entropy, its mixup / cutmix form with top-k and the
-// evaluation accumulator (loss.h), AdamW (adamw.h), the stream
+// and the standalone kernels), the cross-entropy family (label-smoothed, mixup / cutmix targets, top-k)
+// and the evaluation accumulator (loss.h), AdamW (adamw.h), the stream
 // utilities of bench.py, and the library's error string and version.
 #include "ln.h"
 #include "loss.h"
@@ -211,13 +211,52 @@ int tokens_bwd_impl(void* stream, int32_t B, int32_t L, int32_t E, const float* 
 }
 
 // ------------------------------------------------------------------ training loss
-int ce_check(int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype, const int64_t* labels) {
+// One host path for the loss family of loss.h; `what` is the entry point called, so a refusal names
+// it.  mix_labels / ratio both NULL (one label per row) or both set; rank / top both NULL (no
+// metrics: the RANK == false kernels) or both set.  Every refusal returns before any HIP call.
+int ce_check(const char* what, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
+             const int64_t* labels, const int64_t* mix_labels, const float* ratio) {
   if (rows < 1 || rows > SAE_CE_MAX_ROWS || classes < 1 || ld < classes)
-    return fail(SAE_EINVAL, "smoothed_ce: rows %d (1..%d), classes %d, ld %lld", rows, SAE_CE_MAX_ROWS, classes,
+    return fail(SAE_EINVAL, "%s: rows %d (1..%d), classes %d, ld %lld", what, rows, SAE_CE_MAX_ROWS, classes,
                 (long long)ld);
-  if (dtype != SAE_DTYPE_BF16 && dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "smoothed_ce: bad dtype %d", dtype);
-  if (!logits || !labels) return fail(SAE_EINVAL, "smoothed_ce: NULL logits / labels");
+  if (dtype != SAE_DTYPE_BF16 && dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "%s: bad dtype %d", what, dtype);
+  if (!logits || !labels) return fail(SAE_EINVAL, "%s: NULL logits / labels", what);
+  if ((mix_labels == nullptr) != (ratio == nullptr))
+    return fail(SAE_EINVAL, "%s: mix_labels and ratio must both be given or both be NULL", what);
   return 0;
+}
+
+int ce_fwd_impl(const char* what, void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
+                int32_t dtype, const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha,
+                float* lse, float* row_loss, int32_t* rank, float* loss, float* top) {
+  if (int rc = ce_check(what, rows, classes, logits, ld, dtype, labels, mix_labels, ratio)) return rc;
+  if ((rank == nullptr) != (top == nullptr))
+    return fail(SAE_EINVAL, "%s: rank and top must both be given or both be NULL", what);
+  if (!lse || !row_loss || !loss) return fail(SAE_EINVAL, "%s: NULL lse / row_loss / loss", what);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch("ce_fwd", rank ? ce_fwd_kernel<T, true> : ce_fwd_kernel<T, false>, (long long)rows, dim3(256), 0,
+                      st, reinterpret_cast<const T*>(logits), (long long)ld, labels, mix_labels, ratio, classes, alpha,
+                      lse, row_loss, (int*)rank);
+      }))
+    return rc;
+  return launch("ce_mean", rank ? ce_mean_kernel<true> : ce_mean_kernel<false>, 1LL, dim3(256), 0, st,
+                (const float*)row_loss, (const int*)rank, rows, loss, top);
+}
+
+int ce_bwd_impl(const char* what, void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
+                int32_t dtype, const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha,
+                const float* lse, const float* grad_loss, void* dlogits, int64_t ldd) {
+  if (int rc = ce_check(what, rows, classes, logits, ld, dtype, labels, mix_labels, ratio)) return rc;
+  if (!lse || !grad_loss || !dlogits || ldd < classes)
+    return fail(SAE_EINVAL, "%s: NULL lse / grad_loss / dlogits or ldd < classes", what);
+  return by_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return launch("ce_bwd", mix_labels ? ce_bwd_kernel<T, true> : ce_bwd_kernel<T, false>, (long long)rows, dim3(256), 0,
+                  (hipStream_t)stream, reinterpret_cast<const T*>(logits), (long long)ld, labels, mix_labels, ratio, rows,
+                  classes, alpha, lse, grad_loss, reinterpret_cast<T*>(dlogits), (long long)ldd);
+  });
 }
 
 }  // namespace
@@ -302,9 +341,10 @@ int sae_dropout_rows(void* stream, int32_t M, int32_t C, int32_t dtype, const vo
   a.vec = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && !((uintptr_t)x & amask) && !((uintptr_t)y & amask);
   const long long total = (long long)M * ((C + 3) / 4);
   const long long grid = std::min<long long>((total + 255) / 256, 16384);
-  return dtype == SAE_DTYPE_BF16
-             ? launch("dropout_rows", dropout_rows_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, a)
-             : launch("dropout_rows", dropout_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return by_dtype(dtype, [&](auto* t) {
+    return launch("dropout_rows", dropout_rows_kernel<std::remove_pointer_t<decltype(t)>>, grid, dim3(256), 0,
+                  (hipStream_t)stream, a);
+  });
 }
 
 int sae_dropout_rows_mask(void* stream, int32_t M, int32_t C, float rate, const uint64_t* rng, uint32_t stream_id,
@@ -363,75 +403,32 @@ int sae_tokens_bwd_dropout(void* stream, int32_t B, int32_t L, int32_t E, const 
   return tokens_bwd_impl(stream, B, L, E, dx, dtokens, dcls, dpos, &d);
 }
 
-int sae_smoothed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
-                        int32_t dtype, const int64_t* labels, float alpha, float* lse, float* row_loss, float* loss) {
-  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
-  if (!lse || !row_loss || !loss) return fail(SAE_EINVAL, "smoothed_ce_fwd: NULL lse / row_loss / loss");
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = dtype == SAE_DTYPE_BF16
-                     ? launch("smoothed_ce_fwd", smoothed_ce_fwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
-                              reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, classes, alpha, lse, row_loss)
-                     : launch("smoothed_ce_fwd", smoothed_ce_fwd_kernel<float>, (long long)rows, dim3(256), 0, st,
-                              reinterpret_cast<const float*>(logits), (long long)ld, labels, classes, alpha, lse, row_loss);
-  if (rc) return rc;
-  return launch("smoothed_ce_mean", smoothed_ce_mean_kernel, 1LL, dim3(256), 0, st, row_loss, rows, loss);
-}
-
-int sae_smoothed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
-                        int32_t dtype, const int64_t* labels, float alpha, const float* lse,
-                        const float* grad_loss, void* dlogits, int64_t ldd) {
-  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
-  if (!lse || !grad_loss || !dlogits || ldd < classes)
-    return fail(SAE_EINVAL, "smoothed_ce_bwd: NULL lse / grad_loss / dlogits or ldd < classes");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SAE_DTYPE_BF16)
-    return launch("smoothed_ce_bwd", smoothed_ce_bwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
-                  reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, rows, classes, alpha, lse, grad_loss,
-                  reinterpret_cast<__bf16*>(dlogits), (long long)ldd);
-  return launch("smoothed_ce_bwd", smoothed_ce_bwd_kernel<float>, (long long)rows, dim3(256), 0, st,
-                reinterpret_cast<const float*>(logits), (long long)ld, labels, rows, classes, alpha, lse, grad_loss,
-                reinterpret_cast<float*>(dlogits), (long long)ldd);
-}
-
-// mix_labels / ratio both NULL (one label per row) or both set; rank / top both NULL (no metrics) or both set
+// the loss family (ce_fwd_impl / ce_bwd_impl); sae_smoothed_ce_* is sae_mixed_ce_* with the optional arguments NULL
 int sae_mixed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
                      const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha, float* lse,
                      float* row_loss, int32_t* rank, float* loss, float* top) {
-  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
-  if ((mix_labels == nullptr) != (ratio == nullptr))
-    return fail(SAE_EINVAL, "mixed_ce_fwd: mix_labels and ratio must both be given or both be NULL");
-  if ((rank == nullptr) != (top == nullptr))
-    return fail(SAE_EINVAL, "mixed_ce_fwd: rank and top must both be given or both be NULL");
-  if (!lse || !row_loss || !loss) return fail(SAE_EINVAL, "mixed_ce_fwd: NULL lse / row_loss / loss");
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = dtype == SAE_DTYPE_BF16
-                     ? launch("mixed_ce_fwd", mixed_ce_fwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
-                              reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, mix_labels, ratio, classes,
-                              alpha, lse, row_loss, (int*)rank)
-                     : launch("mixed_ce_fwd", mixed_ce_fwd_kernel<float>, (long long)rows, dim3(256), 0, st,
-                              reinterpret_cast<const float*>(logits), (long long)ld, labels, mix_labels, ratio, classes,
-                              alpha, lse, row_loss, (int*)rank);
-  if (rc) return rc;
-  return launch("mixed_ce_mean", mixed_ce_mean_kernel, 1LL, dim3(256), 0, st, (const float*)row_loss,
-                (const int*)rank, rows, loss, top);
+  return ce_fwd_impl("mixed_ce_fwd", stream, rows, classes, logits, ld, dtype, labels, mix_labels, ratio, alpha, lse,
+                     row_loss, rank, loss, top);
 }
 
 int sae_mixed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld, int32_t dtype,
                      const int64_t* labels, const int64_t* mix_labels, const float* ratio, float alpha,
                      const float* lse, const float* grad_loss, void* dlogits, int64_t ldd) {
-  if (int rc = ce_check(rows, classes, logits, ld, dtype, labels)) return rc;
-  if ((mix_labels == nullptr) != (ratio == nullptr))
-    return fail(SAE_EINVAL, "mixed_ce_bwd: mix_labels and ratio must both be given or both be NULL");
-  if (!lse || !grad_loss || !dlogits || ldd < classes)
-    return fail(SAE_EINVAL, "mixed_ce_bwd: NULL lse / grad_loss / dlogits or ldd < classes");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SAE_DTYPE_BF16)
-    return launch("mixed_ce_bwd", mixed_ce_bwd_kernel<__bf16>, (long long)rows, dim3(256), 0, st,
-                  reinterpret_cast<const __bf16*>(logits), (long long)ld, labels, mix_labels, ratio, rows, classes, alpha,
-                  lse, grad_loss, reinterpret_cast<__bf16*>(dlogits), (long long)ldd);
-  return launch("mixed_ce_bwd", mixed_ce_bwd_kernel<float>, (long long)rows, dim3(256), 0, st,
-                reinterpret_cast<const float*>(logits), (long long)ld, labels, mix_labels, ratio, rows, classes, alpha,
-                lse, grad_loss, reinterpret_cast<float*>(dlogits), (long long)ldd);
+  return ce_bwd_impl("mixed_ce_bwd", stream, rows, classes, logits, ld, dtype, labels, mix_labels, ratio, alpha, lse,
+                     grad_loss, dlogits, ldd);
+}
+
+int sae_smoothed_ce_fwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
+                        int32_t dtype, const int64_t* labels, float alpha, float* lse, float* row_loss, float* loss) {
+  return ce_fwd_impl("smoothed_ce_fwd", stream, rows, classes, logits, ld, dtype, labels, nullptr, nullptr, alpha, lse,
+                     row_loss, nullptr, loss, nullptr);
+}
+
+int sae_smoothed_ce_bwd(void* stream, int32_t rows, int32_t classes, const void* logits, int64_t ld,
+                        int32_t dtype, const int64_t* labels, float alpha, const float* lse,
+                        const float* grad_loss, void* dlogits, int64_t ldd) {
+  return ce_bwd_impl("smoothed_ce_bwd", stream, rows, classes, logits, ld, dtype, labels, nullptr, nullptr, alpha, lse,
+                     grad_loss, dlogits, ldd);
 }
 
 static_assert(sizeof(CeAccum) == SAE_CE_ACCUM_BYTES, "the evaluation accumulator is 32 bytes");

@@ -1609,50 +1609,13 @@ def add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, be
 
 
 # ------------------------------------------------------------------------------ training loss
-class _SmoothedCE(torch.autograd.Function):
-    """Label-smoothed softmax cross entropy, mean over rows (train.py:77-90: optax.smooth_labels +
-    jnp.mean(optax.softmax_cross_entropy)) in three HIP launches (sae_smoothed_ce_fwd / _bwd);
-    dlogits come back in the logits' dtype."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, alpha):
-        lib = L.load()
-        R, K = logits.shape
-        lse = torch.empty(R, dtype=torch.float32, device=logits.device)
-        row_loss = torch.empty(R, dtype=torch.float32, device=logits.device)
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        L.check(lib.sae_smoothed_ce_fwd(_stream(logits), R, K, _ptr(logits), logits.stride(0), dtype_code(logits.dtype),
-                                        _ptr(labels), float(alpha), _ptr(lse), _ptr(row_loss), _ptr(loss)))
-        ctx.save_for_backward(logits, labels, lse)
-        ctx.alpha = float(alpha)
-        return loss
-
-    @staticmethod
-    @_sinking
-    def backward(ctx, gloss):
-        lib = L.load()
-        logits, labels, lse = ctx.saved_tensors
-        R, K = logits.shape
-        g = gloss.float().contiguous()
-        dx = torch.empty((R, K), dtype=logits.dtype, device=logits.device)
-        L.check(lib.sae_smoothed_ce_bwd(_stream(logits), R, K, _ptr(logits), logits.stride(0), dtype_code(logits.dtype),
-                                        _ptr(labels), ctx.alpha, _ptr(lse), _ptr(g), _ptr(dx), dx.stride(0)))
-        return dx, None, None
-
-
-def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, alpha: float = 0.1) -> torch.Tensor:
-    """mean_r [lse_r - (1 - alpha) x[r, y_r] - (alpha / K) sum_c x[r, c]] of [R, K] GPU logits (bf16 or
-    fp32) against int64 labels [R]; the HIP kernels, or an error when they cannot take the input."""
-    _require_gpu(logits, labels)
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        logits = logits.reshape(-1, logits.shape[-1]).contiguous()
-    return _SmoothedCE.apply(logits, labels.to(torch.int64).contiguous(), alpha)
-
-
-class _MixedCE(torch.autograd.Function):
-    """The smoothed cross entropy against mixup / cutmix targets (train.py:83-90 with ``mix_labels`` /
-    ``ratio``) and, with ``metrics``, the top-1 / top-5 fractions of utils.topk_correct from the same
-    pass (sae_mixed_ce_fwd / _bwd).  Returns ``(loss, top, row_loss, rank)``: only the loss is
+class _CrossEntropy(torch.autograd.Function):
+    """The training loss: label-smoothed softmax cross entropy, mean over rows (train.py:77-90:
+    optax.smooth_labels + jnp.mean(optax.softmax_cross_entropy)) against the targets ``ratio
+    onehot(labels) + (1 - ratio) onehot(mix_labels)`` -- ``mix_labels`` / ``ratio`` None: one label per
+    row, the plain smoothed loss -- and, with ``metrics``, the top-1 / top-5 fractions of
+    utils.topk_correct from the same pass.  Three HIP launches (sae_mixed_ce_fwd / _bwd); dlogits come
+    back in the logits' dtype.  Returns ``(loss, top, row_loss, rank)``: only the loss is
     differentiable; ``top`` [2], ``row_loss`` [R] and ``rank`` [R] feed the metrics and the evaluation
     accumulator (``top`` / ``rank`` empty without metrics)."""
 
@@ -1690,9 +1653,10 @@ class _MixedCE(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
-def mixed_cross_entropy_rows(logits, labels, mix_labels=None, ratio=None, alpha=0.1, metrics=True):
-    """``mixed_cross_entropy`` with its per-row results: ``(loss, top [2], row_loss [R], rank [R])``, what
-    the evaluation accumulator (``ce_accumulate``) and ``train.topk_correct`` read."""
+def _ce_args(logits, labels, mix_labels, ratio):
+    """What the loss kernels take: GPU logits as [R, K] rows of unit column stride (a row-strided view
+    is read in place), int64 labels [R] and, together or not at all, int64 ``mix_labels`` [R] and
+    fp32 ``ratio`` [R]."""
     _require_gpu(logits, labels, mix_labels, ratio)
     if (mix_labels is None) != (ratio is None):
         raise ValueError("mixed_cross_entropy: mix_labels and ratio go together (both or neither)")
@@ -1707,18 +1671,30 @@ def mixed_cross_entropy_rows(logits, labels, mix_labels=None, ratio=None, alpha=
             raise ValueError(f"mixed_cross_entropy: mix_labels / ratio need one entry per row ({R})")
     if labels.numel() != R:
         raise ValueError(f"mixed_cross_entropy: labels need one entry per row ({R})")
-    return _MixedCE.apply(logits, labels, mix_labels, ratio, alpha, bool(metrics))
+    return logits, labels, mix_labels, ratio
+
+
+def mixed_cross_entropy_rows(logits, labels, mix_labels=None, ratio=None, alpha=0.1, metrics=True):
+    """``mixed_cross_entropy`` with its per-row results: ``(loss, top [2], row_loss [R], rank [R])``, what
+    the evaluation accumulator (``ce_accumulate``) and ``train.topk_correct`` read."""
+    return _CrossEntropy.apply(*_ce_args(logits, labels, mix_labels, ratio), alpha, bool(metrics))
 
 
 def mixed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, mix_labels: Optional[torch.Tensor] = None,
                         ratio: Optional[torch.Tensor] = None, alpha: float = 0.1, metrics: bool = False):
     """The smoothed cross entropy of [R, K] GPU logits (bf16 or fp32) against the targets
     ``ratio onehot(labels) + (1 - ratio) onehot(mix_labels)`` (``mix_labels`` int [R], ``ratio`` float
-    [R]; both None: one label per row, bit-identical to ``smoothed_cross_entropy``).  ``metrics=True``
+    [R]; both None: one label per row, ``smoothed_cross_entropy``).  ``metrics=True``
     returns ``(loss, top1, top5)``: the fractions of rows whose first label is among the 1 / 5 largest
     logits in stable-argsort order (0-d device tensors, not differentiable)."""
     loss, top, _, _ = mixed_cross_entropy_rows(logits, labels, mix_labels, ratio, alpha, metrics)
     return (loss, top[0], top[1]) if metrics else loss
+
+
+def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, alpha: float = 0.1) -> torch.Tensor:
+    """mean_r [lse_r - (1 - alpha) x[r, y_r] - (alpha / K) sum_c x[r, c]] of [R, K] GPU logits (bf16 or
+    fp32) against int64 labels [R]: ``mixed_cross_entropy`` with one label per row."""
+    return mixed_cross_entropy(logits, labels, alpha=alpha)
 
 
 def ce_accumulate(row_loss: torch.Tensor, rank: torch.Tensor, acc: torch.Tensor) -> None:

@@ -106,25 +106,9 @@ def _check_clip(clip_grad):
     return None if clip_grad is None else float(clip_grad)
 
 
-def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.1) -> torch.Tensor:
-    """train.py:77-90 (optax.smooth_labels + mean softmax cross entropy): on the GPU the two-launch
-    HIP loss (ops.smoothed_cross_entropy); CPU tensors (the multi-process gloo tests' small
-    models) take torch's cross entropy, which computes the same quantity."""
-    if logits.is_cuda:
-        return ops.smoothed_cross_entropy(logits, labels, smoothing)
-    return F.cross_entropy(logits.float(), labels, label_smoothing=smoothing)
-
-
-def label_ranks(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """Per row, the number of classes a stable ascending argsort of the row (jnp.argsort of
-    utils.topk_correct) places above the row's label: class c is above label y iff x[c] > x[y], or
-    x[c] is NaN and x[y] is not, or they compare equal (-0 == +0; both NaN) and c > y.  A label
-    outside [0, K) ranks K.  GPU logits: the rank the loss kernel counts (sae_mixed_ce_fwd); CPU
-    tensors: the same rule in torch ops.  int32 [R]."""
-    logits = logits.reshape(-1, logits.shape[-1])
-    if logits.is_cuda:
-        return ops.mixed_cross_entropy_rows(logits.detach(), labels, None, None, 0.0, True)[3]
-    x = logits.detach().float()
+def _label_ranks_cpu(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """``label_ranks`` of CPU tensors: the rule the loss kernel counts by, in torch ops."""
+    x = logits.detach().float().reshape(-1, logits.shape[-1])
     K = x.shape[1]
     y = labels.reshape(-1).to(torch.int64)
     ok = (y >= 0) & (y < K)
@@ -134,6 +118,57 @@ def label_ranks(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     cls = torch.arange(K)[None, :]
     above = ((x > xy) | (nx & ~ny) | (((x == xy) | (nx & ny)) & (cls > yc))).sum(1)
     return torch.where(ok, above, torch.full_like(above, K)).to(torch.int32)
+
+
+def _cross_entropy_rows(logits, labels, mix_labels=None, ratio=None, smoothing=0.1, metrics=False):
+    """The one loss of this module, ``(loss, top, row_loss, rank)`` as ops.mixed_cross_entropy_rows
+    returns them: train.py:83-90 (the targets ``ratio onehot(labels) + (1 - ratio) onehot(mix_labels)``,
+    or one label per row when ``mix_labels`` / ``ratio`` are None; optax.smooth_labels; mean softmax
+    cross entropy) and, with ``metrics``, the per-row losses, the first label's ranks (``label_ranks``)
+    and ``top`` = the mean top-1 / top-5 of train.py:98-99.  GPU logits take the HIP loss; CPU tensors
+    (the multi-process gloo tests' small models) take torch's cross entropy, which computes the same
+    quantity: index targets without a partner, probability targets with one.  The HIP loss gives a
+    label outside [0, K) no target term; the CPU branch with a partner refuses one (ValueError).
+    Without ``metrics`` the CPU branch returns None for the other three."""
+    if logits.is_cuda:
+        return ops.mixed_cross_entropy_rows(logits, labels, mix_labels, ratio, smoothing, metrics)
+    if (mix_labels is None) != (ratio is None):
+        raise ValueError("mixed_cross_entropy: mix_labels and ratio go together (both or neither)")
+    x = logits.float()
+    target = labels.to(torch.int64)
+    if mix_labels is not None:
+        K = x.shape[-1]
+        for name, y in (("labels", labels), ("mix_labels", mix_labels)):
+            if bool(((y < 0) | (y >= K)).any()):
+                raise ValueError(f"mixed_cross_entropy (CPU): {name} outside [0, {K})")
+        rho = ratio.to(x.dtype)[:, None]
+        partner = F.one_hot(mix_labels.to(torch.int64), K).to(x.dtype)
+        target = rho * F.one_hot(target, K).to(x.dtype) + (1.0 - rho) * partner
+    loss = F.cross_entropy(x, target, label_smoothing=smoothing)
+    if not metrics:
+        return loss, None, None, None
+    row_loss = F.cross_entropy(x, target, label_smoothing=smoothing, reduction="none")
+    rank = _label_ranks_cpu(logits, labels)
+    return loss, torch.stack([(rank < 1).float().mean(), (rank < 5).float().mean()]), row_loss, rank
+
+
+def smoothed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.1) -> torch.Tensor:
+    """train.py:77-90 (optax.smooth_labels + mean softmax cross entropy): ``mixed_cross_entropy`` with
+    one label per row and no metrics."""
+    return _cross_entropy_rows(logits, labels, None, None, smoothing, False)[0]
+
+
+def label_ranks(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """Per row, the number of classes a stable ascending argsort of the row (jnp.argsort of
+    utils.topk_correct) places above the row's label: class c is above label y iff x[c] > x[y], or
+    x[c] is NaN and x[y] is not, or they compare equal (-0 == +0; both NaN) and c > y.  A label
+    outside [0, K) ranks K.  GPU logits: the rank the loss kernel counts (sae_mixed_ce_fwd); CPU
+    tensors: the same rule in torch ops (alone: torch's cross entropy refuses a label outside the
+    classes).  int32 [R]."""
+    logits = logits.reshape(-1, logits.shape[-1])
+    if logits.is_cuda:
+        return _cross_entropy_rows(logits.detach(), labels, None, None, 0.0, True)[3]
+    return _label_ranks_cpu(logits, labels)
 
 
 def topk_correct(logits: torch.Tensor, labels: torch.Tensor, topk=(1, 5)):
@@ -148,29 +183,11 @@ def mixed_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, mix_labels: 
                         ratio: Optional[torch.Tensor] = None, smoothing: float = 0.1, metrics: bool = False):
     """train.py:83-90 with the default augmentation's mixup / cutmix targets: ``ratio onehot(labels) +
     (1 - ratio) onehot(mix_labels)``, optax.smooth_labels, mean softmax cross entropy.  ``mix_labels``
-    and ``ratio`` go together; both None is the one-label loss.  ``metrics=True`` returns ``(loss, top1,
-    top5)`` with the mean of ``topk_correct`` on the first label (train.py:98-99).  GPU logits take the
-    HIP loss (ops.mixed_cross_entropy); CPU tensors (the multi-process gloo tests' small models) take
-    torch's cross entropy with probability targets, which computes the same quantity.  The HIP loss
-    gives a label outside [0, K) no target term; the CPU branch refuses one (ValueError)."""
-    if logits.is_cuda:
-        return ops.mixed_cross_entropy(logits, labels, mix_labels, ratio, smoothing, metrics)
-    if (mix_labels is None) != (ratio is None):
-        raise ValueError("mixed_cross_entropy: mix_labels and ratio go together (both or neither)")
-    x = logits.float()
-    K = x.shape[-1]
-    for name, y in (("labels", labels), ("mix_labels", mix_labels)):
-        if y is not None and bool(((y < 0) | (y >= K)).any()):
-            raise ValueError(f"mixed_cross_entropy (CPU): {name} outside [0, {K})")
-    target = F.one_hot(labels.to(torch.int64), K).to(x.dtype)
-    if mix_labels is not None:
-        rho = ratio.to(x.dtype)[:, None]
-        target = rho * target + (1.0 - rho) * F.one_hot(mix_labels.to(torch.int64), K).to(x.dtype)
-    loss = F.cross_entropy(x, target, label_smoothing=smoothing)
-    if not metrics:
-        return loss
-    top1, top5 = topk_correct(logits, labels)
-    return loss, top1.mean(), top5.mean()
+    and ``ratio`` go together; both None is the one-label loss, ``smoothed_cross_entropy``.
+    ``metrics=True`` returns ``(loss, top1, top5)`` with the mean of ``topk_correct`` on the first label
+    (train.py:98-99).  Devices and refusals: ``_cross_entropy_rows``."""
+    loss, top, _, _ = _cross_entropy_rows(logits, labels, mix_labels, ratio, smoothing, metrics)
+    return (loss, top[0], top[1]) if metrics else loss
 
 
 def init_distributed():
@@ -723,7 +740,7 @@ class TrainStep:
                 loss = mixed_cross_entropy(logits, labels, mix_labels, ratio, self.smoothing, self.metrics)
                 if self.metrics:
                     loss, self._top1, self._top5 = loss
-            else:
+            else:   # the same loss (_cross_entropy_rows), named by the module global tools/ab_loss.sh replaces
                 loss = smoothed_cross_entropy(logits, labels, self.smoothing)
             # world > 1: the SUM all-reduce of the per-rank gradients of loss / world is the
             # gradient of the global-batch mean (survey D9)
@@ -981,12 +998,10 @@ class EvalStep:
                 logits = self.model(images, is_training=False)
             else:
                 logits = self.model(images, is_training=False, layout=self.input_layout)
+            loss, _, row_loss, rank = _cross_entropy_rows(logits, labels, None, None, 0.0, True)
             if logits.is_cuda:
-                loss, _, row_loss, rank = ops.mixed_cross_entropy_rows(logits, labels, None, None, 0.0, True)
                 ops.ce_accumulate(row_loss, rank, self._acc)
                 return loss
-            row_loss = F.cross_entropy(logits.float(), labels.to(torch.int64), reduction="none")
-            rank = label_ranks(logits, labels)
             loss_sum, counts = ops.ce_accumulator_fields(self._acc)
             loss_sum += row_loss.double().sum()
             counts += torch.stack([(rank < 1).sum(), (rank < 5).sum(), torch.tensor(rank.numel())])

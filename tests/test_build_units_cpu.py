@@ -47,3 +47,23 @@ def test_one_definition_per_kernel():
     assert not dup, dup
     lib_stubs = {n for n in _nm(B.OUT) if STUB in n}
     assert lib_stubs == stubs, (sorted(lib_stubs - stubs), sorted(stubs - lib_stubs))
+
+
+def test_the_loss_is_one_kernel_family():
+    """misc.hip holds the loss once (csrc/loss.h): ce_fwd_kernel<{__bf16, float}, {false, true}>,
+    ce_mean_kernel<{false, true}>, ce_bwd_kernel<{__bf16, float}, {false, true}> (split on MIX after
+    the timing check, profiles/loss_unify_ab.txt) and ce_accumulate_kernel, and no second copy of the
+    formula for the one-label case (no kernel named smoothed_ce)."""
+    (obj,) = [o for o in _objects() if os.path.basename(o) == "misc.hip.o"]
+    syms = set(_nm(obj))
+    assert not [n for n in syms if "smoothed_ce" in n and not n.startswith("sae_smoothed_ce_")]
+    assert {"sae_smoothed_ce_fwd", "sae_smoothed_ce_bwd", "sae_mixed_ce_fwd", "sae_mixed_ce_bwd"} <= syms
+    # Itanium names: sae::<kernel><template arguments>; DF16b is __bf16, f float, Lb0E / Lb1E false / true
+    got = set()
+    for n in syms:
+        m = re.match(r"_ZN3sae\d+((?:[a-z0-9]+_)*ce_[a-z_]+_kernel)(?:I((?:DF16b|f)?(?:Lb[01]E)?)E)?Ev?", n)
+        if m and STUB not in n:
+            got.add((m.group(1), m.group(2) or ""))
+    want = {(k, t + r) for k in ("ce_fwd_kernel", "ce_bwd_kernel") for t in ("DF16b", "f") for r in ("Lb0E", "Lb1E")}
+    want |= {("ce_mean_kernel", "Lb0E"), ("ce_mean_kernel", "Lb1E"), ("ce_accumulate_kernel", "")}
+    assert got == want, (sorted(got - want), sorted(want - got))

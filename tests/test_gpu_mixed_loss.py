@@ -7,6 +7,10 @@ tests/test_gpu_loss.py holds the one-label arithmetic to (loss 1e-5 relative; dl
 max|grad| for fp32 logits, one bf16 rounding 2^-8 for bf16 logits).  Bit-exactness against
 ``ops.smoothed_cross_entropy`` without a partner label and with ratio == 1.  Top-k: exact on every row
 against ``np.argsort(kind="stable")``, under heavy ties, NaN and -0."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -62,8 +66,11 @@ def _loss_and_grad(fn, x):
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("alpha", [0.1, 0.0])
 def test_mixed_ce_bit_exact_against_one_label_loss(dev, dt, alpha):
-    """No partner label, and ratio == 1 with any partner: the bits of ops.smoothed_cross_entropy, loss
-    and gradient; also on a row-strided view, and on a second call."""
+    """No partner label, ratio == 1 with any partner, and metrics=True: the bits of
+    ops.smoothed_cross_entropy, loss and gradient; also on a row-strided view, and on a second call.
+    ops.smoothed_cross_entropy is the no-partner form, so these pairs compare the kernels' paths with
+    each other (RANK off / on, mix NULL / set); test_ce_bits_are_the_parent_kernels below holds them all
+    to recorded bits."""
     from sae_vision_amd import ops
     for R, K in SHAPES:
         x, y0, y1, _ = _mix_case(dev, R, K, dt, 7 * R + K)
@@ -104,6 +111,76 @@ def test_mixed_ce_bit_exact_against_one_label_loss(dev, dt, alpha):
     assert torch.equal(la, lb) and torch.equal(ga, gb)
     assert torch.equal(la, lc) and torch.equal(ga, gc)
     assert not torch.equal(ga, g0)                             # the partner labels were felt
+
+
+def _ce_bits():
+    """tests/golden/make_ce_bits.py as a module: the cases, their seeded inputs and the digest."""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_ce_bits.py")
+    spec = importlib.util.spec_from_file_location("make_ce_bits", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _smoothed_ce_c_abi(x, y0, alpha, upstream):
+    """``(loss, row_loss, dlogits)`` from sae_smoothed_ce_fwd / _bwd called directly."""
+    import sae_vision_amd
+    from sae_vision_amd import _lib as L
+    lib = sae_vision_amd.load_library()
+    R, K = x.shape
+    f32 = dict(dtype=torch.float32, device=x.device)
+    lse, row_loss, loss = torch.empty(R, **f32), torch.empty(R, **f32), torch.empty((), **f32)
+    g = torch.tensor(upstream, **f32)
+    dx = torch.empty(R, K, dtype=x.dtype, device=x.device)
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    code = L.SAE_DTYPE_BF16 if x.dtype == torch.bfloat16 else L.SAE_DTYPE_F32
+    L.check(lib.sae_smoothed_ce_fwd(st, R, K, x.data_ptr(), x.stride(0), code, y0.data_ptr(), alpha, lse.data_ptr(),
+                                    row_loss.data_ptr(), loss.data_ptr()))
+    L.check(lib.sae_smoothed_ce_bwd(st, R, K, x.data_ptr(), x.stride(0), code, y0.data_ptr(), alpha, lse.data_ptr(),
+                                    g.data_ptr(), dx.data_ptr(), dx.stride(0)))
+    return loss, row_loss, dx
+
+
+def test_ce_bits_are_the_parent_kernels(dev):
+    """Every form of the one-label loss -- ops.smoothed_cross_entropy, the mixed loss without a partner,
+    with ratio == 1, with metrics=True, and the sae_smoothed_ce_* entry points called directly -- gives
+    the loss, row losses and dlogits whose SHA-256 digests tests/golden/ce_parent_bits.json records:
+    the bits of the separate smoothed_ce_* kernels the loss had before it became one family.
+
+    The file is made by tests/golden/make_ce_bits.py, which uses only API older than that change.  When
+    the toolchain changes the bits, regenerate it on the PARENT of the toolchain bump (check that
+    commit out, build it with the new toolchain, run the script there, copy the file here): never from
+    the code under test."""
+    from sae_vision_amd import ops
+    M = _ce_bits()
+    with open(os.path.join(os.path.dirname(M.__file__), "ce_parent_bits.json")) as f:
+        doc = json.load(f)
+    keys = []
+    for key, R, K, pitch, dt, alpha in M.cases():
+        keys.append(key)
+        want = doc["cases"][key]
+        x, y0, y1 = M.case_inputs(dev, R, K, pitch, dt)
+        ones = torch.ones(R, device=dev)
+
+        def rows(mix, ratio, metrics):
+            """(loss, row_loss, dlogits) of one form of ops.mixed_cross_entropy_rows"""
+            kept = []
+
+            def fn(t):
+                out = ops.mixed_cross_entropy_rows(t, y0, mix, ratio, alpha, metrics)
+                kept.append(out[2])
+                return out[0]
+            loss, dx = M.loss_and_grad(fn, x)
+            return loss, kept[0], dx
+
+        l0, g0 = M.loss_and_grad(lambda t: ops.smoothed_cross_entropy(t, y0, alpha), x)
+        forms = {"smoothed": (l0, None, g0), "no partner": rows(None, None, False), "ratio 1": rows(y1, ones, False),
+                 "metrics": rows(None, None, True), "C ABI": _smoothed_ce_c_abi(x, y0, alpha, M.UPSTREAM)}
+        for form, got in forms.items():
+            for name, t in zip(("loss", "row_loss", "dlogits"), got):
+                if t is not None:
+                    assert M.digest(t) == want[name], (key, form, name)
+    assert sorted(keys) == sorted(doc["cases"]) and doc["upstream_gradient"] == M.UPSTREAM
 
 
 def _stable_topk(x: np.ndarray, y: np.ndarray, k: int) -> np.ndarray:

@@ -130,6 +130,26 @@ def test_new_entry_points_validate_on_the_host():
     assert L.SAE_CE_ACCUM_BYTES == 32
 
 
+def test_a_refusal_names_the_entry_point_called():
+    """sae_smoothed_ce_* forwards to the host path of sae_mixed_ce_*; each refusal still names the
+    function the caller called (no GPU touched: the refusals return before any HIP call)."""
+    import sae_vision_amd
+    from sae_vision_amd import _lib as L
+    lib = sae_vision_amd.load_library()
+    d = ctypes.c_void_p(256)
+    err = lambda: lib.sae_last_error().decode()
+    assert lib.sae_smoothed_ce_fwd(None, 0, 10, d, 10, L.SAE_DTYPE_BF16, d, 0.1, d, d, d) == L.SAE_EINVAL
+    assert err().startswith("smoothed_ce_fwd:") and "rows 0" in err()
+    assert lib.sae_mixed_ce_fwd(None, 0, 10, d, 10, L.SAE_DTYPE_BF16, d, None, None, 0.1, d, d, None, d, None) == L.SAE_EINVAL
+    assert err().startswith("mixed_ce_fwd:") and "rows 0" in err()
+    assert lib.sae_smoothed_ce_bwd(None, 8, 10, d, 10, L.SAE_DTYPE_F32, d, 0.1, d, d, d, 9) == L.SAE_EINVAL
+    assert err().startswith("smoothed_ce_bwd:") and "ldd < classes" in err()
+    assert lib.sae_mixed_ce_bwd(None, 8, 10, d, 10, 7, d, None, None, 0.1, d, d, d, 10) == L.SAE_EINVAL
+    assert err().startswith("mixed_ce_bwd:") and "bad dtype 7" in err()
+    assert lib.sae_smoothed_ce_fwd(None, 8, 10, d, 10, L.SAE_DTYPE_BF16, d, 0.1, None, d, d) == L.SAE_EINVAL
+    assert err().startswith("smoothed_ce_fwd:") and "NULL lse" in err()
+
+
 def test_step_refuses_mismatched_mix_arguments():
     from sae_vision_amd import train
     from test_dp_gloo import TinyNet, _data

@@ -4,9 +4,10 @@ metrics, inside ONE process (cdna_hip_programming.md §5.4 rule 24): the two var
 over several rounds, median ms/step each and the round-to-round spread of each.
 
     python tools/mixed_loss_ab.py [--rounds 6] [--steps 20] [--batch 128]
-Variants: ``plain`` (TrainStep(graph=True): sae_smoothed_ce_fwd / _bwd) and ``mixed``
-(TrainStep(graph=True, mix=True, metrics=True): sae_mixed_ce_fwd / _bwd with partner labels, ratios
-and the top-1 / top-5 ranks).  Each variant trains its own copy of the model from the same start.
+Variants of the one loss family (csrc/loss.h, sae_mixed_ce_fwd / _bwd): ``plain`` (TrainStep(graph=True):
+no partner labels, no ranks -- the special case sae_smoothed_ce_* names; ce_fwd_kernel<T, false>) and
+``mixed`` (TrainStep(graph=True, mix=True, metrics=True): partner labels, ratios and the top-1 / top-5
+ranks; ce_fwd_kernel<T, true>).  Each variant trains its own copy of the model from the same start.
 Output: profiles/mixed_loss_ab.txt.
 """
 import argparse
