@@ -425,6 +425,47 @@ int sae_layernorm_bwd_dropout(void* stream, int32_t M, int32_t C, const float* x
                               void* workspace, float rate, const uint64_t* rng, uint32_t stream_id,
                               int64_t row0, int64_t row_step);
 
+/* The CvT convolutional projection in front of its 1x1 convolution (cvt_attention.py:12-40):
+   depthwise 3x3 convolution (stride 1 or 2, Flax SAME padding: Ho = ceil(H / stride), total padding
+   max((Ho - 1) stride + 3 - H, 0) with the smaller half in front) followed by BatchNorm.
+     t[b,p,q,c] = sum_{i,j} xpad[b, p stride + i, q stride + j, c] w[i,j,c]   (fp32 accumulation, i outer,
+                  j inner, rounded to the compute dtype)
+     training:   mu, var = biased statistics of t over N = B Ho Wo positions (fp64 sums, no
+                 cancellation for a large mean), rstd = rsqrt(var + eps),
+                 y = ((t - mu) rstd) gamma + beta, and the Flax running averages
+                 run_mean = momentum run_mean + (1 - momentum) mu, run_var likewise with var
+                 (updated on the device, stream-ordered: a captured graph advances them per replay)
+     evaluation: the same formula with run_mean / run_var in one kernel; t, mean, rstd and workspace
+                 may be NULL and the running buffers are not written.
+   x [B][H][W][C], t and y [B][Ho][Wo][C] contiguous in the compute dtype (bf16 or fp32); w fp32
+   [3][3][C] (the Flax kernel [3, 3, 1, C]; rounded to the compute dtype as it is loaded); gamma,
+   beta, run_mean, run_var, mean, rstd fp32 [C].  channels must be a multiple of 8 (bf16) or 4
+   (fp32); every pointer 16-byte aligned.  Every reduction has a fixed order (no atomics): two calls
+   on the same inputs agree bit for bit. */
+typedef struct sae_dwconv_desc {
+  int32_t batch, height, width, channels;
+  int32_t stride;    /* 1 or 2 */
+  int32_t dtype;     /* SAE_DTYPE_* */
+  int32_t training;  /* 0: evaluation (running statistics), else batch statistics */
+  float momentum;    /* of the running averages (Flax convention) */
+  float eps;
+} sae_dwconv_desc;
+/* Bytes sae_dwconv_bn_fwd / _bwd need at `workspace` for either compute dtype (0: unsupported shape):
+   the per-workgroup partial rows of the reductions and, for the backward, dt (B Ho Wo C elements). */
+size_t sae_dwconv_bn_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride);
+int sae_dwconv_bn_fwd(void* stream, const sae_dwconv_desc* desc, const void* x, const float* w,
+                      const float* gamma, const float* beta, float* run_mean, float* run_var, void* t,
+                      void* y, float* mean, float* rstd, void* workspace);
+/* Backward of the training form, from the t, mean, rstd the forward saved and g = dy:
+     dbeta = sum g, dgamma = sum g xhat, dt = gamma rstd (g - dbeta / N - xhat dgamma / N),
+     dx[b,h,w,c] = sum over taps (i,j) and outputs (p,q) with p stride + i = h + pad_top,
+                   q stride + j = w + pad_left of w[i,j,c] dt[b,p,q,c]   (gather; compute dtype),
+     dw[i,j,c] = sum_{b,p,q} xpad[b, p stride + i, q stride + j, c] dt[b,p,q,c]   (fp32 [3][3][C]).
+   dw, dgamma, dbeta are overwritten.  desc->training == 0 is SAE_EUNSUPPORTED. */
+int sae_dwconv_bn_bwd(void* stream, const sae_dwconv_desc* desc, const void* x, const float* w,
+                      const float* gamma, const void* t, const float* mean, const float* rstd,
+                      const void* dy, void* dx, float* dw, float* dgamma, float* dbeta, void* workspace);
+
 /* Optimizer update of the data-parallel training step (train.py:25-27,229-233: optax.adamw,
    survey D9 descent), every parameter in ONE launch.  The parameters are cut into chunks of
    SAE_ADAMW_CHUNK elements; sae_adamw_plan (host only, no GPU call) fills that chunk table for

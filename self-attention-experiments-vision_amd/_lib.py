@@ -51,8 +51,17 @@ class SaeAttnDesc(ctypes.Structure):
     ]
 
 
+class SaeDwconvDesc(ctypes.Structure):
+    """Mirror of ``sae_dwconv_desc`` (include/sae_attn.h)."""
+    _fields_ = [("batch", _i32), ("height", _i32), ("width", _i32), ("channels", _i32), ("stride", _i32),
+                ("dtype", _i32), ("training", _i32), ("momentum", _f32), ("eps", _f32)]
+
+
 # (name, restype, argtypes) for every entry point declared in include/sae_attn.h
 _PROTOS = [
+    ("sae_dwconv_bn_workspace_bytes", _sz, [_i32] * 5),
+    ("sae_dwconv_bn_fwd", _i32, [_vp, ctypes.POINTER(SaeDwconvDesc)] + [_vp] * 11),
+    ("sae_dwconv_bn_bwd", _i32, [_vp, ctypes.POINTER(SaeDwconvDesc)] + [_vp] * 12),
     ("sae_attn_desc_init", None, [ctypes.POINTER(SaeAttnDesc), _i32, _i32, _i32, _i32, _i32, _i32, _f32]),
     ("sae_attn_fwd", _i32, [_vp, ctypes.POINTER(SaeAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("sae_attn_bwd_workspace_bytes", _sz, [ctypes.POINTER(SaeAttnDesc)]),

@@ -1,9 +1,11 @@
 // misc.hip -- the rest of the C ABI: residual add + LayerNorm (ln.h), the encoder input tokens
 // (tokens.h), the hidden-state dropout of row-major activations (drop_rows.h: their dropout forms
 // and the standalone kernels), the cross-entropy family (label-smoothed, mixup / cutmix targets, top-k)
-// and the evaluation accumulator (loss.h), AdamW (adamw.h), the stream
-// utilities of bench.py, and the library's error string and version.
+// and the evaluation accumulator (loss.h), AdamW (adamw.h), the CvT convolutional projection
+// (depthwise 3x3 + BatchNorm, dwconv.h), the stream utilities of bench.py, and the library's error
+// string and version.
 #include "ln.h"
+#include "dwconv.h"
 #include "loss.h"
 #include "tokens.h"
 #include "adamw.h"
@@ -259,6 +261,118 @@ int ce_bwd_impl(const char* what, void* stream, int32_t rows, int32_t classes, c
   });
 }
 
+
+// ------------------------------------------------- depthwise 3x3 convolution + BatchNorm (CvT)
+// The launch geometry of dwconv.h for one element type (V channels per 16-byte vector).  Partial
+// rows cost workspace traffic (16 bytes per channel and workgroup for the fp64 pairs, 36 for dw), so
+// the grids are capped: 1024 workgroups, and for the dw pass as many as keep its partials near 4 MB.
+constexpr int kDwMaxBlocks = 1024;
+
+struct DwGrid {
+  int chunks, fwd, pix, dx, dw;
+};
+
+int dw_blocks(long long work, int per_block, int cap) {
+  return (int)std::max<long long>(1, std::min<long long>((work + per_block - 1) / per_block, cap));
+}
+
+DwGrid dw_geometry(const sae_dwconv_desc& d, int V, DwConvArgs& a) {
+  const int s = d.stride;
+  a.B = d.batch;
+  a.H = d.height;
+  a.W = d.width;
+  a.C = d.channels;
+  a.Ho = (a.H + s - 1) / s;
+  a.Wo = (a.W + s - 1) / s;
+  a.pt = std::max((a.Ho - 1) * s + 3 - a.H, 0) / 2;   // Flax SAME: the smaller half in front
+  a.pl = std::max((a.Wo - 1) * s + 3 - a.W, 0) / 2;
+  const int CV = a.C / V;
+  a.CVt = std::min(CV, 256);
+  a.PS = 256 / a.CVt;
+  a.rpr = (a.Wo + kDwRun - 1) / kDwRun;
+  a.nruns = a.B * a.Ho * a.rpr;
+  a.rpr_in = (a.W + kDwRun - 1) / kDwRun;
+  a.nruns_in = a.B * a.H * a.rpr_in;
+  a.npix = (long long)a.B * a.Ho * a.Wo;
+  a.momentum = d.momentum;
+  a.eps = d.eps;
+  DwGrid g;
+  g.chunks = (CV + a.CVt - 1) / a.CVt;
+  g.fwd = dw_blocks(a.nruns, a.PS, kDwMaxBlocks);
+  g.pix = dw_blocks(a.npix, a.PS * kDwPix, kDwMaxBlocks);
+  g.dx = dw_blocks(a.nruns_in, a.PS, kDwMaxBlocks);
+  g.dw = dw_blocks(a.nruns, a.PS, std::max(256, std::min(kDwMaxBlocks, (4 << 20) / (36 * a.C))));
+  return g;
+}
+
+// bytes of the partial rows (a multiple of 16: C % 4 == 0); the backward's dt follows them
+size_t dw_partial_bytes(const sae_dwconv_desc& d, int V) {
+  DwConvArgs a;
+  const DwGrid g = dw_geometry(d, V, a);
+  return std::max((size_t)std::max(g.fwd, g.pix) * 2 * a.C * sizeof(double), (size_t)g.dw * 9 * a.C * sizeof(float));
+}
+
+size_t dw_workspace(const sae_dwconv_desc& d, int V) {
+  DwConvArgs a;
+  dw_geometry(d, V, a);
+  return dw_partial_bytes(d, V) + (size_t)a.npix * a.C * (V == 8 ? 2 : 4);
+}
+
+// everything but the pointers; every refusal returns before any HIP call
+int dw_check(const char* what, const sae_dwconv_desc* d) {
+  if (!d) return fail(SAE_EINVAL, "%s: NULL descriptor", what);
+  if (d->batch < 1 || d->height < 1 || d->width < 1 || d->channels < 1)
+    return fail(SAE_EINVAL, "%s: batch %d, height %d, width %d, channels %d must be >= 1", what, d->batch, d->height,
+                d->width, d->channels);
+  if (d->dtype != SAE_DTYPE_BF16 && d->dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "%s: bad dtype %d", what, d->dtype);
+  if (d->stride != 1 && d->stride != 2) return fail(SAE_EUNSUPPORTED, "%s: stride %d (1 or 2)", what, d->stride);
+  const int V = d->dtype == SAE_DTYPE_BF16 ? 8 : 4;
+  if (d->channels % V)
+    return fail(SAE_EUNSUPPORTED, "%s: channels %d must be a multiple of %d in %s", what, d->channels, V,
+                d->dtype == SAE_DTYPE_BF16 ? "bf16" : "fp32");
+  if ((long long)d->batch * d->height * d->width > (1LL << 30))
+    return fail(SAE_EUNSUPPORTED, "%s: batch * height * width > 2^30", what);
+  return SAE_OK;
+}
+
+template <typename T>
+int dw_fwd_launch(hipStream_t st, const sae_dwconv_desc& d, DwConvArgs& a) {
+  const DwGrid g = dw_geometry(d, DwVec<T>::N, a);
+  const dim3 gf((unsigned)g.fwd, (unsigned)g.chunks), gp((unsigned)g.pix, (unsigned)g.chunks);
+  if (!d.training)
+    return launch("dwconv_bn_eval", d.stride == 1 ? dwconv_fwd_kernel<T, 1, false> : dwconv_fwd_kernel<T, 2, false>, gf,
+                  dim3(256), 0, st, a);
+  a.nparts = g.fwd;
+  if (int rc = launch("dwconv_fwd", d.stride == 1 ? dwconv_fwd_kernel<T, 1, true> : dwconv_fwd_kernel<T, 2, true>, gf,
+                      dim3(256), 0, st, a))
+    return rc;
+  if (int rc = launch("dwconv_stats", dwconv_reduce_kernel<double, true>, (long long)(a.C + kDwRedC - 1) / kDwRedC, dim3(256), 0, st,
+                      a, a.C, (float*)nullptr, (float*)nullptr, 0))
+    return rc;
+  return launch("dwconv_norm", dwconv_norm_kernel<T>, gp, dim3(256), 0, st, a);
+}
+
+template <typename T>
+int dw_bwd_launch(hipStream_t st, const sae_dwconv_desc& d, DwConvArgs& a) {
+  const DwGrid g = dw_geometry(d, DwVec<T>::N, a);
+  const dim3 gp((unsigned)g.pix, (unsigned)g.chunks), gx((unsigned)g.dx, (unsigned)g.chunks),
+      gw((unsigned)g.dw, (unsigned)g.chunks);
+  a.nparts = g.pix;
+  if (int rc = launch("dwconv_bwd_sums", dwconv_bwd_sums_kernel<T>, gp, dim3(256), 0, st, a)) return rc;
+  if (int rc = launch("dwconv_bwd_sums_reduce", dwconv_reduce_kernel<double, false>, (long long)(2 * a.C + kDwRedC - 1) / kDwRedC,
+                      dim3(256), 0, st, a, 2 * a.C, a.dbeta, a.dgamma, a.C))
+    return rc;
+  a.nparts = g.dw;
+  a.dt = reinterpret_cast<char*>(a.part) + dw_partial_bytes(d, DwVec<T>::N);
+  if (int rc = launch("dwconv_dw", d.stride == 1 ? dwconv_dw_kernel<T, 1> : dwconv_dw_kernel<T, 2>, gw, dim3(256), 0, st, a))
+    return rc;
+  if (int rc = launch("dwconv_dw_reduce", dwconv_reduce_kernel<float, false>, (long long)(9 * a.C + kDwRedC - 1) / kDwRedC,
+                      dim3(256), 0, st, a, 9 * a.C, a.dw, (float*)nullptr, 9 * a.C))
+    return rc;
+  void (*const fx[3])(DwConvArgs) = {dwconv_dx_kernel<T, 1, 1>, dwconv_dx_kernel<T, 2, 0>, dwconv_dx_kernel<T, 2, 1>};
+  return launch("dwconv_dx", fx[d.stride == 1 ? 0 : 1 + a.pl], gx, dim3(256), 0, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -440,6 +554,81 @@ int sae_ce_accumulate(void* stream, int32_t rows, const float* row_loss, const i
   if ((uintptr_t)acc & 7) return fail(SAE_EINVAL, "ce_accumulate: acc must be 8-byte aligned");
   return launch("ce_accumulate", ce_accumulate_kernel, 1LL, dim3(256), 0, (hipStream_t)stream, row_loss,
                 (const int*)rank, rows, reinterpret_cast<CeAccum*>(acc));
+}
+
+// ------------------------------------------------- depthwise 3x3 convolution + BatchNorm (CvT)
+size_t sae_dwconv_bn_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride) {
+  if (B < 1 || H < 1 || W < 1 || C < 1 || C % 4 || (stride != 1 && stride != 2) || (long long)B * H * W > (1LL << 30))
+    return 0;
+  sae_dwconv_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = B;
+  d.height = H;
+  d.width = W;
+  d.channels = C;
+  d.stride = stride;
+  return std::max(dw_workspace(d, 4), C % 8 ? (size_t)0 : dw_workspace(d, 8));   // either element type
+}
+
+int sae_dwconv_bn_fwd(void* stream, const sae_dwconv_desc* desc, const void* x, const float* w, const float* gamma,
+                      const float* beta, float* run_mean, float* run_var, void* t, void* y, float* mean, float* rstd,
+                      void* workspace) {
+  if (int rc = dw_check("dwconv_bn_fwd", desc)) return rc;
+  if (!x || !w || !gamma || !beta || !run_mean || !run_var || !y)
+    return fail(SAE_EINVAL, "dwconv_bn_fwd: NULL x / w / gamma / beta / run_mean / run_var / y");
+  if (desc->training && (!t || !mean || !rstd || !workspace))
+    return fail(SAE_EINVAL, "dwconv_bn_fwd: training needs t, mean, rstd and workspace");
+  if (!aligned16(x) || !aligned16(w) || !aligned16(gamma) || !aligned16(beta) || !aligned16(run_mean) ||
+      !aligned16(run_var) || !aligned16(t) || !aligned16(y) || !aligned16(mean) || !aligned16(rstd) ||
+      !aligned16(workspace))
+    return fail(SAE_EINVAL, "dwconv_bn_fwd: every pointer needs 16-byte alignment");
+  DwConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.w = w;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.run_mean = run_mean;
+  a.run_var = run_var;
+  a.t = t;
+  a.y = y;
+  a.mean = mean;
+  a.rstd = rstd;
+  a.part = workspace;
+  return by_dtype(desc->dtype, [&](auto* p) {
+    return dw_fwd_launch<std::remove_pointer_t<decltype(p)>>((hipStream_t)stream, *desc, a);
+  });
+}
+
+int sae_dwconv_bn_bwd(void* stream, const sae_dwconv_desc* desc, const void* x, const float* w, const float* gamma,
+                      const void* t, const float* mean, const float* rstd, const void* dy, void* dx, float* dw,
+                      float* dgamma, float* dbeta, void* workspace) {
+  if (int rc = dw_check("dwconv_bn_bwd", desc)) return rc;
+  if (!desc->training)
+    return fail(SAE_EUNSUPPORTED, "dwconv_bn_bwd: training = 0 (the evaluation form has no backward)");
+  if (!x || !w || !gamma || !t || !mean || !rstd || !dy || !dx || !dw || !dgamma || !dbeta || !workspace)
+    return fail(SAE_EINVAL, "dwconv_bn_bwd: NULL argument");
+  if (!aligned16(x) || !aligned16(w) || !aligned16(gamma) || !aligned16(t) || !aligned16(mean) || !aligned16(rstd) ||
+      !aligned16(dy) || !aligned16(dx) || !aligned16(dw) || !aligned16(dgamma) || !aligned16(dbeta) ||
+      !aligned16(workspace))
+    return fail(SAE_EINVAL, "dwconv_bn_bwd: every pointer needs 16-byte alignment");
+  DwConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.w = w;
+  a.gamma = gamma;
+  a.t = const_cast<void*>(t);
+  a.mean = const_cast<float*>(mean);
+  a.rstd = const_cast<float*>(rstd);
+  a.dy = dy;
+  a.dx = dx;
+  a.dw = dw;
+  a.dgamma = dgamma;
+  a.dbeta = dbeta;
+  a.part = workspace;
+  return by_dtype(desc->dtype, [&](auto* p) {
+    return dw_bwd_launch<std::remove_pointer_t<decltype(p)>>((hipStream_t)stream, *desc, a);
+  });
 }
 
 // ---------------------------------------------------------------------------------- AdamW

@@ -4,8 +4,10 @@
 ``(inputs_q [b, H, W, c], inputs_kv [b, H', W', c], is_training)`` and param tree
 (``ConvProjectionBlock_{0,1,2}/{Conv_0, BatchNorm_0, Conv_1}``, ``TalkingHeadsBlock_{0,1}``,
 ``DenseGeneral_0``).  The convolutional projections (depthwise 3x3 + BatchNorm + 1x1,
-cvt_attention.py:21-40) are outside the hot path (conv, not attention) and run as
-framework convolutions; the attention core with Nq != Nk -- the query keeps the full grid
+cvt_attention.py:21-40) run the depthwise convolution and the BatchNorm on the HIP kernels of
+``ops.dwconv_bn`` (3x3 kernels, stride 1 / 2, C % 8 == 0 in bf16 or C % 4 == 0 in fp32; other
+calls keep the framework route, ``ConvProjectionBlock._framework_forward``) and the 1x1
+convolution on ``ops.dense``; the attention core with Nq != Nk -- the query keeps the full grid
 (stride 1), keys and values are strided (2, 2) -- runs on the fused HIP kernels
 (``ops.attention`` / ``ops.talking_heads_attention``), and the output projection on ``ops.dense``.
 """
@@ -73,6 +75,18 @@ class ConvProjectionBlock(nn.Module):
         self.Conv_1 = _Conv(1, in_ch, out_ch, use_bias, device)
 
     def forward(self, x, is_training):   # x [b, H, W, c] -> [b, H', W', out]
+        bn = self.BatchNorm_0
+        wants_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in (
+            self.Conv_0.kernel, bn.scale, bn.bias)))
+        if not ops.dwconv_bn_ok(x, self.kernel_size, self.strides, self.dtype, is_training, wants_grad):
+            return self._framework_forward(x, is_training)
+        # depthwise conv + BatchNorm in HIP (ops.dwconv_bn; it moves bn.mean / bn.var itself)
+        y = ops.dwconv_bn(x, self.Conv_0.kernel, bn.scale, bn.bias, bn.mean, bn.var, self.strides, bn.momentum,
+                          bn.eps, is_training, self.dtype)
+        return ops.dense(y, self.Conv_1.kernel.reshape(x.shape[-1], -1), self.Conv_1.bias, self.dtype)
+
+    def _framework_forward(self, x, is_training):
+        """The same projection as framework ops: every shape ``ops.dwconv_bn_ok`` refuses."""
         dt, k, s = self.dtype, self.kernel_size, self.strides
         c = x.shape[-1]
         xc = x.to(dt)                                                   # [b, H, W, c]

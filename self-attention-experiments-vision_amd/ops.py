@@ -27,7 +27,8 @@ __all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "wei
            "clear_weight_cache", "gemm_dw", "layer_norm", "add_layer_norm", "dropout_rows", "dropout_rows_mask",
            "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed",
            "relpos_bias", "rotary", "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer",
-           "DenseFacts", "dense_facts_of_shapes", "dense_fwd_plan", "dense_bwd_plan"]
+           "DenseFacts", "dense_facts_of_shapes", "dense_fwd_plan", "dense_bwd_plan",
+           "dwconv_bn", "dwconv_bn_ok", "same_pads"]
 
 
 class KernelTimer:
@@ -1845,3 +1846,112 @@ def cls_add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor
     ``dropout``: as :func:`add_layer_norm`, with the class rows' slice of the full tensor's mask."""
     _require_gpu(x, delta, gamma, beta)
     return _ClsAddLayerNorm.apply(x, delta, gamma, beta, eps, _draw(dropout))
+
+
+# ------------------------------------------------- CvT projection: depthwise 3x3 conv + BatchNorm
+def same_pads(n: int, k: int, s: int) -> Tuple[int, int]:
+    """Flax ``SAME`` padding (low, high) of an axis of length ``n`` for kernel ``k``, stride ``s``:
+    output ceil(n / s), total max((out - 1) s + k - n, 0), the smaller half in front."""
+    out = -(-n // s)
+    total = max((out - 1) * s + k - n, 0)
+    return total // 2, total - total // 2
+
+
+def dwconv_bn_ok(x, kernel_size: int, stride: int, dtype: torch.dtype, training: bool = True,
+                 needs_grad: Optional[bool] = None) -> bool:
+    """Host predicate of :func:`dwconv_bn` (``sae_dwconv_bn_*``): a GPU tensor [B, H, W, C], a 3 x 3
+    kernel, stride 1 or 2, bf16 with C % 8 == 0 or fp32 with C % 4 == 0.  The evaluation form has no
+    backward: with a gradient wanted (``needs_grad``; default: ``x.requires_grad`` under grad mode)
+    it is not taken."""
+    if not getattr(x, "is_cuda", False) or len(x.shape) != 4:
+        return False
+    if kernel_size != 3 or stride not in (1, 2) or dtype not in (torch.bfloat16, torch.float32):
+        return False
+    if x.shape[-1] % (8 if dtype == torch.bfloat16 else 4) or min(x.shape) < 1:
+        return False
+    if x.shape[0] * x.shape[1] * x.shape[2] > 1 << 30:
+        return False
+    if needs_grad is None:
+        needs_grad = torch.is_grad_enabled() and bool(x.requires_grad)
+    return bool(training) or not needs_grad
+
+
+def _dwconv_desc(x, stride, momentum, eps, training) -> L.SaeDwconvDesc:
+    B, H, W, C = x.shape
+    return L.SaeDwconvDesc(B, H, W, C, int(stride), dtype_code(x.dtype), 1 if training else 0, float(momentum),
+                           float(eps))
+
+
+class _DwConvBn(torch.autograd.Function):
+    """``sae_dwconv_bn_fwd`` / ``_bwd``: saves the conv output t and the batch mean / rstd; the running
+    buffers are advanced by the forward's kernels (stream-ordered, no host read)."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, run_mean, run_var, stride, momentum, eps, training):
+        lib = L.load()
+        B, H, W, C = x.shape
+        d = _dwconv_desc(x, stride, momentum, eps, training)
+        Ho, Wo = -(-H // stride), -(-W // stride)
+        y = torch.empty((B, Ho, Wo, C), dtype=x.dtype, device=x.device)
+        t = mean = rstd = ws = None
+        if training:
+            t = torch.empty_like(y)
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.sae_dwconv_bn_workspace_bytes(B, H, W, C, int(stride)), dtype=torch.uint8,
+                             device=x.device)
+        tok = _TIMER.begin("dwconv_bn_fwd") if _TIMER is not None else None
+        L.check(lib.sae_dwconv_bn_fwd(_stream(x), ctypes.byref(d), _ptr(x), _ptr(w), _ptr(gamma), _ptr(beta),
+                                      _ptr(run_mean), _ptr(run_var), _ptr(t), _ptr(y), _ptr(mean), _ptr(rstd),
+                                      _ptr(ws)))
+        if tok is not None:
+            _TIMER.end(tok, (B, H, W, C, stride))
+        ctx.training = training
+        if training:
+            ctx.save_for_backward(x, w, gamma, t, mean, rstd)
+            ctx.desc = d
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.training:
+            raise RuntimeError("dwconv_bn: the evaluation form has no backward (dwconv_bn_ok refuses it)")
+        lib = L.load()
+        x, w, gamma, t, mean, rstd = ctx.saved_tensors
+        d = ctx.desc
+        B, H, W, C = x.shape
+        dy = dy.to(x.dtype).contiguous()
+        dx = torch.empty_like(x)
+        dw = torch.empty((3, 3, 1, C), dtype=torch.float32, device=x.device)
+        dg = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.sae_dwconv_bn_workspace_bytes(B, H, W, C, d.stride), dtype=torch.uint8, device=x.device)
+        tok = _TIMER.begin("dwconv_bn_bwd") if _TIMER is not None else None
+        L.check(lib.sae_dwconv_bn_bwd(_stream(x), ctypes.byref(d), _ptr(x), _ptr(w), _ptr(gamma), _ptr(t), _ptr(mean),
+                                      _ptr(rstd), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(dg), _ptr(db), _ptr(ws)))
+        if tok is not None:
+            _TIMER.end(tok, (B, H, W, C, d.stride))
+        return dx, dw, dg, db, None, None, None, None, None, None
+
+
+def dwconv_bn(x: torch.Tensor, w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, run_mean: torch.Tensor,
+              run_var: torch.Tensor, stride: int, momentum: float, eps: float, training: bool,
+              dtype: torch.dtype) -> torch.Tensor:
+    """Depthwise 3 x 3 convolution (Flax SAME padding, ``stride`` 1 or 2) + BatchNorm of ``x``
+    [B, H, W, C] in the compute dtype ``dtype`` -> [B, ceil(H / s), ceil(W / s), C]
+    (cvt_attention.py:21-36).  ``w`` is the Flax depthwise kernel [3, 3, 1, C] (fp32; used at
+    ``dtype``), ``gamma`` / ``beta`` the BatchNorm scale / bias, ``run_mean`` / ``run_var`` its fp32
+    batch_stats buffers: training normalises with the biased batch statistics and moves the buffers in
+    place (ra = momentum * ra + (1 - momentum) * batch), evaluation reads them.  Gradients of x, w,
+    gamma, beta.  No host synchronisation: the call can be captured into a graph."""
+    _require_gpu(x, w, gamma, beta, run_mean, run_var)
+    if not dwconv_bn_ok(x, w.shape[0], stride, dtype):
+        raise ValueError(f"dwconv_bn: unsupported call (x {tuple(x.shape)}, kernel {tuple(w.shape)}, stride {stride}, "
+                         f"{dtype}); see dwconv_bn_ok")
+    if run_mean.dtype != torch.float32 or run_var.dtype != torch.float32 or not run_mean.is_contiguous() \
+            or not run_var.is_contiguous():
+        raise ValueError("dwconv_bn: run_mean / run_var must be contiguous fp32 buffers (they are updated in place)")
+    x = x.to(dtype)
+    x = x if x.is_contiguous() else x.contiguous()
+    return _DwConvBn.apply(x, _f32c(w, "w"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), run_mean, run_var, int(stride),
+                           float(momentum), float(eps), bool(training))
