@@ -4,7 +4,9 @@ Each ``torch.autograd.Function`` below is a thin host-side shim: it allocates ou
 the framework's caching allocator, fills an ``sae_attn_desc`` with the tensors' element
 strides, and calls the HIP library on the current stream.  Forward saves the log-sum-exp
 rows, never the [B, H, Nq, Nk] probabilities (the reference materialises them:
-models/layers/attentions/attention.py:41-58).
+models/layers/attentions/attention.py:41-58).  There is one Function per kernel family:
+``_Attention`` and ``_TalkingHeads`` take q, k, v or one packed projection, ``_LayerNorm`` serves
+every residual add + LayerNorm form; the public functions select its mode and outputs.
 
 The public functions are the names in ``__all__``; each one's docstring cites the reference lines it
 restates.  A Dense projection's routes are planned by ``dense_fwd_plan`` / ``dense_bwd_plan``.
@@ -291,6 +293,11 @@ def _draw(dropout):
     return (float(rate), rng.state, rng.next_stream())
 
 
+def _drop_args(drop):
+    """The three C arguments (rate, state pointer, stream id) of a drawn dropout triple."""
+    return drop[0], _ptr(drop[1]), drop[2]
+
+
 # ------------------------------------------------------------------- hidden-state dropout
 def dropout_rows_mask(M: int, C: int, rate: float, rng: DropoutRng, stream_id: int, row0: int = 0,
                       row_step: int = 1) -> torch.Tensor:
@@ -309,7 +316,7 @@ def _dropout_rows_call(x2, y2, drop):
     lib = L.load()
     M, C = x2.shape
     L.check(lib.sae_dropout_rows(_stream(x2), M, C, dtype_code(x2.dtype), _ptr(x2), x2.stride(0), _ptr(y2),
-                                 y2.stride(0), drop[0], _ptr(drop[1]), drop[2], 0, 1))
+                                 y2.stride(0), *_drop_args(drop), 0, 1))
 
 
 class _DropoutRows(torch.autograd.Function):
@@ -348,6 +355,7 @@ def dropout_rows(x: torch.Tensor, dropout=None) -> torch.Tensor:
     return _DropoutRows.apply(x, _draw(dropout))
 
 
+# ---------------------------------------------------------------------------- attention core
 def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None, drop=None):
     lib = L.load()
     B, Nq, H, D = q.shape
@@ -361,7 +369,7 @@ def _fwd(q, k, v, scale, bias_h=None, bias_w=None, grid=None, rope=None, drop=No
                                         _ptr(cos), _ptr(o), _ptr(lse)))
     elif drop is not None:
         L.check(lib.sae_attn_fwd_dropout(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
-                                         drop[0], _ptr(drop[1]), drop[2]))
+                                         *_drop_args(drop)))
     else:
         L.check(lib.sae_attn_fwd(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(bias_h),
                                  _ptr(bias_w), _ptr(o), _ptr(lse)))
@@ -384,8 +392,7 @@ def _bwd(q, k, v, o, lse, do, dq, dk, dv, scale, bias_h=None, bias_w=None, grid=
                                         _ptr(do), _ptr(sin), _ptr(cos), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws)))
     elif drop is not None:
         L.check(lib.sae_attn_bwd_dropout(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
-                                         _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), drop[0], _ptr(drop[1]),
-                                         drop[2]))
+                                         _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), *_drop_args(drop)))
     else:
         L.check(lib.sae_attn_bwd(_stream(q), ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
                                  _ptr(do), _ptr(bias_h), _ptr(bias_w), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dbh),
@@ -399,11 +406,31 @@ def _grad_in(g: torch.Tensor) -> torch.Tensor:
     return g if g.stride(-1) == 1 else g.contiguous()
 
 
+def _split(q, k, v):
+    """(q, k, v) of a call: three tensors, or -- ``k`` and ``v`` None -- the three views of ``q``, a
+    packed projection [B, N, 3, H, D]."""
+    return (q[:, :, 0], q[:, :, 1], q[:, :, 2]) if k is None else (q, k, v)
+
+
+def _qkv_grads(q, k, v):
+    """Where a backward writes dq / dk / dv, and what autograd gets back for (q, k, v): three
+    tensors, or ONE buffer for a packed projection, written through the strides of its three views
+    (no per-view gradient accumulation passes)."""
+    if k is None:
+        dqkv = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        return _split(dqkv, None, None), (dqkv, None, None)
+    grads = tuple(torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (q, k, v))
+    return grads, grads
+
+
 class _Attention(torch.autograd.Function):
+    """The attention core on q, k, v [B, N, H, D], or on a packed projection ``q`` [B, N, 3, H, D]
+    with ``k`` and ``v`` None."""
+
     @staticmethod
     def forward(ctx, q, k, v, scale, bias_h, bias_w, grid, rope, drop):
         _require_gpu(q, k, v)
-        o, lse = _fwd(q, k, v, scale, bias_h, bias_w, grid, rope, drop)
+        o, lse = _fwd(*_split(q, k, v), scale, bias_h, bias_w, grid, rope, drop)
         ctx.save_for_backward(q, k, v, o, lse, bias_h, bias_w)
         ctx.scale, ctx.grid, ctx.rope, ctx.drop = scale, grid, rope, drop
         return o
@@ -413,32 +440,9 @@ class _Attention(torch.autograd.Function):
     def backward(ctx, do):
         q, k, v, o, lse, bias_h, bias_w = ctx.saved_tensors
         do = _grad_in(do)
-        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        dk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
-        dv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        dbh, dbw = _bwd(q, k, v, o, lse, do, dq, dk, dv, ctx.scale, bias_h, bias_w, ctx.grid, ctx.rope, ctx.drop)
-        return dq, dk, dv, None, dbh, dbw, None, None, None
-
-
-class _AttentionPacked(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, scale, rope, drop):
-        _require_gpu(qkv)
-        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
-        o, lse = _fwd(q, k, v, scale, rope=rope, drop=drop)
-        ctx.save_for_backward(qkv, o, lse)
-        ctx.scale, ctx.rope, ctx.drop = scale, rope, drop
-        return o
-
-    @staticmethod
-    @_sinking
-    def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
-        do = _grad_in(do)
-        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
-        _bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2],
-             ctx.scale, rope=ctx.rope, drop=ctx.drop)
-        return dqkv, None, None, None
+        grads, ret = _qkv_grads(q, k, v)
+        dbh, dbw = _bwd(*_split(q, k, v), o, lse, do, *grads, ctx.scale, bias_h, bias_w, ctx.grid, ctx.rope, ctx.drop)
+        return (*ret, None, dbh, dbw, None, None, None)
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
@@ -455,22 +459,14 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional
     standalone pass, and relative logits are not supported with it."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if dropout is not None:
-        if bias is not None:
-            raise NotImplementedError("attention dropout with relative logits is not implemented")
-        if rotary is not None:
-            q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))
-        return _Attention.apply(q, k, v, float(scale), None, None, None, None, _draw(dropout))
-    if rotary is not None and bias is None:
-        if rope_fused_ok(q, k, v):
-            return _Attention.apply(q, k, v, float(scale), None, None, None, float(rotary), None)
-        q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))
-    elif rotary is not None:
-        q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))
-    if bias is None:
-        return _Attention.apply(q, k, v, float(scale), None, None, None, None, None)
-    bh, bw, grid = bias
-    return _Attention.apply(q, k, v, float(scale), bh, bw, tuple(grid), None, None)
+    if dropout is not None and bias is not None:
+        raise NotImplementedError("attention dropout with relative logits is not implemented")
+    if rotary is not None and (dropout is not None or bias is not None or not rope_fused_ok(q, k, v)):
+        q, k = _Rotary.apply(q, float(rotary)), _Rotary.apply(k, float(rotary))   # the standalone pass
+        rotary = None
+    bh, bw, grid = (None, None, None) if bias is None else (bias[0], bias[1], tuple(bias[2]))
+    return _Attention.apply(q, k, v, float(scale), bh, bw, grid, None if rotary is None else float(rotary),
+                            _draw(dropout))
 
 
 def attention_packed(qkv: torch.Tensor, scale: Optional[float] = None, rotary: Optional[float] = None,
@@ -483,9 +479,8 @@ def attention_packed(qkv: torch.Tensor, scale: Optional[float] = None, rotary: O
         scale = 1.0 / math.sqrt(qkv.shape[-1])
     if rotary is not None and (dropout is not None or not rope_fused_ok(qkv[:, :, 0])):
         return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale, rotary=rotary, dropout=dropout)
-    if dropout is not None:
-        return _AttentionPacked.apply(qkv, float(scale), None, _draw(dropout))
-    return _AttentionPacked.apply(qkv, float(scale), None if rotary is None else float(rotary), None)
+    return _Attention.apply(qkv, None, None, float(scale), None, None, None, None if rotary is None else float(rotary),
+                            _draw(dropout))
 
 
 # ----------------------------------------------------------------------------- talking heads
@@ -549,10 +544,13 @@ def _th_sinks(th1, th2):
 
 
 class _TalkingHeads(torch.autograd.Function):
+    """Talking-heads attention on q, k, v [B, N, H, D], or on a packed projection ``q``
+    [B, N, 3, H, D] with ``k`` and ``v`` None."""
+
     @staticmethod
     def forward(ctx, q, k, v, th1, th2, scale, rope):
         _require_gpu(q, k, v, th1, th2)
-        o, lse, th1c, th2c = _th_fwd(q, k, v, th1, th2, scale, rope)
+        o, lse, th1c, th2c = _th_fwd(*_split(q, k, v), th1, th2, scale, rope)
         ctx.save_for_backward(q, k, v, th1c, th2c, lse)
         ctx.scale, ctx.rope = scale, rope
         ctx.th_dtypes = (th1.dtype, th2.dtype)
@@ -564,39 +562,11 @@ class _TalkingHeads(torch.autograd.Function):
     def backward(ctx, do):
         q, k, v, th1, th2, lse = ctx.saved_tensors
         do = _grad_in(do)
-        dq, dk, dv = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (q, k, v))
+        grads, ret = _qkv_grads(q, k, v)
         s1, s2 = ctx.sinks
-        dth1, dth2 = _th_bwd(q, k, v, th1, th2, lse, do, dq, dk, dv, ctx.scale, ctx.rope,
+        dth1, dth2 = _th_bwd(*_split(q, k, v), th1, th2, lse, do, *grads, ctx.scale, ctx.rope,
                              _grad_out(s1, th1.shape, th1.device), _grad_out(s2, th2.shape, th2.device))
-        return (dq, dk, dv, _unsunk(dth1.to(ctx.th_dtypes[0]), s1), _unsunk(dth2.to(ctx.th_dtypes[1]), s2), None,
-                None)
-
-
-class _TalkingHeadsPacked(torch.autograd.Function):
-    """Talking heads on the packed projection [B, N, 3, H, D]: dq / dk / dv land in ONE gradient
-    buffer through strides (no per-view gradient accumulation passes)."""
-
-    @staticmethod
-    def forward(ctx, qkv, th1, th2, scale, rope):
-        _require_gpu(qkv, th1, th2)
-        o, lse, th1c, th2c = _th_fwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], th1, th2, scale, rope)
-        ctx.save_for_backward(qkv, th1c, th2c, lse)
-        ctx.scale, ctx.rope = scale, rope
-        ctx.th_dtypes = (th1.dtype, th2.dtype)
-        ctx.sinks = _th_sinks(th1, th2)
-        return o
-
-    @staticmethod
-    @_sinking
-    def backward(ctx, do):
-        qkv, th1, th2, lse = ctx.saved_tensors
-        do = _grad_in(do)
-        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
-        s1, s2 = ctx.sinks
-        dth1, dth2 = _th_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], th1, th2, lse, do, dqkv[:, :, 0],
-                             dqkv[:, :, 1], dqkv[:, :, 2], ctx.scale, ctx.rope,
-                             _grad_out(s1, th1.shape, th1.device), _grad_out(s2, th2.shape, th2.device))
-        return dqkv, _unsunk(dth1.to(ctx.th_dtypes[0]), s1), _unsunk(dth2.to(ctx.th_dtypes[1]), s2), None, None
+        return (*ret, _unsunk(dth1.to(ctx.th_dtypes[0]), s1), _unsunk(dth2.to(ctx.th_dtypes[1]), s2), None, None)
 
 
 def _th_rope_ok(q, k, v) -> bool:
@@ -613,7 +583,7 @@ def talking_heads_attention_packed(qkv, th1, th2, scale: Optional[float] = None,
     q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
     if rotary is not None and not _th_rope_ok(q, k, v):
         return talking_heads_attention(q, k, v, th1, th2, scale, rotary)
-    return _TalkingHeadsPacked.apply(qkv, th1, th2, float(scale), None if rotary is None else float(rotary))
+    return _TalkingHeads.apply(qkv, None, None, th1, th2, float(scale), None if rotary is None else float(rotary))
 
 
 def talking_heads_attention(q, k, v, th1, th2, scale: Optional[float] = None, rotary: Optional[float] = None):
@@ -1354,8 +1324,7 @@ def gemm_nt(a2: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = N
         if epilogue != EPI_GELU_GRAD:
             raise ValueError("gemm_nt: dropout rides in the EPI_GELU_GRAD epilogue only")
         L.check(lib.sae_gemm_nt_gelu_dropout(_stream(a2), M, N, K, _ptr(a2), a2.stride(0), _ptr(bt), bt.stride(0),
-                                             _ptr(bias), _ptr(c), c.stride(0), _ptr(c2), drop[0], _ptr(drop[1]),
-                                             drop[2]))
+                                             _ptr(bias), _ptr(c), c.stride(0), _ptr(c2), *_drop_args(drop)))
         return c, c2
     L.check(lib.sae_gemm_nt(_stream(a2), M, N, K, _ptr(a2), a2.stride(0), _ptr(bt), bt.stride(0), _ptr(bias),
                             _ptr(c), c.stride(0), int(epilogue), _ptr(aux), aux.stride(0) if aux is not None else 0,
@@ -1436,7 +1405,7 @@ def layer_norm_ok(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == torch.float32 and C % 4 == 0 and C <= 1024 and x.is_contiguous()
 
 
-def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
+def _f32c(t: torch.Tensor) -> torch.Tensor:
     """fp32 contiguous view/copy of a LayerNorm operand (the kernels read raw fp32)."""
     if t.dtype != torch.float32:
         t = t.float()
@@ -1450,9 +1419,23 @@ def _bf16c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _ln_fwd(x, delta, gamma, beta, eps, drop=None, rows=(0, 1)):
+class _LnScale(NamedTuple):
+    """The scaled (CaiT) form of the residual add, ``x + delta * bf16(ls[c]) * rowscale[row // rpb]``."""
+    ls: torch.Tensor                       # fp32 contiguous copy of the LayerScale parameter
+    rowscale: Optional[torch.Tensor]       # fp32 [B], or None
+    rpb: int                               # rows per sample
+    delta: Optional[torch.Tensor] = None   # backward: the bf16 addend the forward read
+    sink: Optional[torch.Tensor] = None    # backward: the LayerScale gradient's sink
+
+
+def _ln_fwd(x, delta, gamma, beta, eps, drop=None, rows=(0, 1), scaled: Optional[_LnScale] = None):
+    """sae_layernorm_fwd, its dropout form (the addend dropped as it is added, with the mask of rows
+    rows[0] + i * rows[1]) or its scaled form -> ``(x + delta, y, mean, rstd)``; without an addend the
+    first is None."""
+    if drop is not None and scaled is not None:
+        raise NotImplementedError("layer norm: the dropout form has no LayerScale")
     lib = L.load()
-    x, gamma, beta = _f32c(x, "x"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
+    x, gamma, beta = _f32c(x), _f32c(gamma), _f32c(beta)
     if delta is not None:
         delta = _bf16c(delta)
     C = x.shape[-1]
@@ -1461,124 +1444,127 @@ def _ln_fwd(x, delta, gamma, beta, eps, drop=None, rows=(0, 1)):
     mean = torch.empty(M, dtype=torch.float32, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
     xout = torch.empty_like(x) if delta is not None else None
-    if drop is not None:   # the addend dropped as it is added: mask rows rows[0] + i * rows[1]
-        L.check(lib.sae_layernorm_fwd_dropout(_stream(x), M, C, _ptr(x), _ptr(delta), _ptr(xout), _ptr(gamma),
-                                              _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), float(eps), drop[0],
-                                              _ptr(drop[1]), drop[2], int(rows[0]), int(rows[1])))
-        return xout, y, mean, rstd
-    L.check(lib.sae_layernorm_fwd(_stream(x), M, C, _ptr(x), _ptr(delta), _ptr(xout), _ptr(gamma), _ptr(beta),
-                                  _ptr(y), _ptr(mean), _ptr(rstd), float(eps)))
+    args = (_stream(x), M, C, _ptr(x), _ptr(delta), _ptr(xout), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean),
+            _ptr(rstd), float(eps))
+    if drop is not None:
+        L.check(lib.sae_layernorm_fwd_dropout(*args, *_drop_args(drop), int(rows[0]), int(rows[1])))
+    elif scaled is not None:
+        L.check(lib.sae_layernorm_fwd_scaled(*args, _ptr(scaled.ls), _ptr(scaled.rowscale), int(scaled.rpb)))
+    else:
+        L.check(lib.sae_layernorm_fwd(*args))
     return xout, y, mean, rstd
 
 
-def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None), drop=None, rows=(0, 1)):
+def _ln_bwd(xs, mean, rstd, gamma, dy, dxin, want_ddelta, sinks=(None, None), drop=None, rows=(0, 1),
+            scaled: Optional[_LnScale] = None):
+    """sae_layernorm_bwd, its dropout form (ddelta = bf16(dx * keep / pk): the forward's mask) or its
+    scaled form -> ``(dx, ddelta, dgamma, dbeta, dlayerscale)``; ``dxin`` (the residual stream's
+    gradient, added into dx) may be None, ddelta is None unless wanted, dlayerscale unless scaled."""
+    if drop is not None and scaled is not None:
+        raise NotImplementedError("layer norm: the dropout form has no LayerScale")
     lib = L.load()
     C = xs.shape[-1]
     M = xs.numel() // C
-    xs, gamma = _f32c(xs, "x"), _f32c(gamma, "gamma")
+    xs, gamma = _f32c(xs), _f32c(gamma)
     dy = _bf16c(dy)
     dx = torch.empty_like(xs)
     ddelta = torch.empty(xs.shape, dtype=torch.bfloat16, device=xs.device) if want_ddelta else None
     dg = _grad_out(sinks[0], (C,), xs.device)
     db = _grad_out(sinks[1], (C,), xs.device)
+    dls = _grad_out(scaled.sink, (C,), xs.device) if scaled is not None else None
     ws = torch.empty(lib.sae_layernorm_bwd_workspace_bytes(M, C), dtype=torch.uint8, device=xs.device)
     if dxin is not None:
-        dxin = _f32c(dxin, "dxin")
-    if drop is not None:   # ddelta = bf16(dx * keep / pk): the forward's mask
-        L.check(lib.sae_layernorm_bwd_dropout(_stream(xs), M, C, _ptr(xs), _ptr(mean), _ptr(rstd), _ptr(gamma),
-                                              _ptr(dy), _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db),
-                                              _ptr(ws), drop[0], _ptr(drop[1]), drop[2], int(rows[0]), int(rows[1])))
-        return dx, ddelta, dg, db
-    L.check(lib.sae_layernorm_bwd(_stream(xs), M, C, _ptr(xs), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dy),
-                                  _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db), _ptr(ws)))
-    return dx, ddelta, dg, db
+        dxin = _f32c(dxin)
+    args = (_stream(xs), M, C, _ptr(xs), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dy), _ptr(dxin), _ptr(dx),
+            _ptr(ddelta), _ptr(dg), _ptr(db), _ptr(ws))
+    if drop is not None:
+        L.check(lib.sae_layernorm_bwd_dropout(*args, *_drop_args(drop), int(rows[0]), int(rows[1])))
+    elif scaled is not None:
+        L.check(lib.sae_layernorm_bwd_scaled(*args, _ptr(scaled.delta), _ptr(scaled.ls), _ptr(scaled.rowscale),
+                                             int(scaled.rpb), _ptr(dls)))
+    else:
+        L.check(lib.sae_layernorm_bwd(*args))
+    return dx, ddelta, dg, db, dls
+
+
+def _cls_rows(rows: torch.Tensor, shape, dtype) -> torch.Tensor:
+    """Zeros of ``shape`` [B, N, E] whose class-token rows [:, 0] are ``rows`` [B, E]."""
+    out = torch.zeros(shape, dtype=dtype, device=rows.device)
+    out[:, 0] = rows
+    return out
 
 
 class _LayerNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        _, y, mean, rstd = _ln_fwd(x, None, gamma, beta, eps)
-        ctx.save_for_backward(x, mean, rstd, gamma)
-        ctx.sinks = (_sink(gamma), _sink(beta))
-        return y
+    """The one LayerNorm of the fp32 residual stream: ``(stream, y)`` with y = LN(stream) in bf16 and
+    stream = x, or x + delta for a bf16 addend (dropped as it is added under ``drop``; times
+    ``ls[c] * rowscale[sample]``, the CaiT blocks' LayerScale and stochastic-depth factor, when ``ls`` is
+    given).  Returning the stream lets the backward add the residual gradient inside the LayerNorm
+    backward kernel (dx = dstream + LN'^T dy) instead of autograd summing the two paths in a separate
+    pass; a caller that has no use for it says ``stream=False`` and gets None in its place, and the
+    kernel then runs with dxin = NULL.  ``cls``: the class-token rows of x, delta [B, N, E] only -> y
+    [B, E] (ViT's head reads token 0, vit.py:95; LayerNorm is row-wise, so those rows' values equal the
+    full pass's, and under dropout they take their slice, rows b * N, of the full tensor's mask); the
+    backward writes the class rows of dx and ddelta, the other rows take no gradient from here."""
 
     @staticmethod
-    @_sinking
-    def backward(ctx, dy):
-        x, mean, rstd, gamma = ctx.saved_tensors
-        dx, _, dg, db = _ln_bwd(x, mean, rstd, gamma, dy, None, False, ctx.sinks)
-        return dx, _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None
-
-
-class _AddLayerNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, delta, gamma, beta, eps, drop=None):
-        xout, y, mean, rstd = _ln_fwd(x, delta, gamma, beta, eps, drop)
-        ctx.save_for_backward(xout, mean, rstd, gamma)
-        ctx.delta_dtype, ctx.drop = delta.dtype, drop
-        ctx.sinks = (_sink(gamma), _sink(beta))
-        return xout, y
-
-    @staticmethod
-    @_sinking
-    def backward(ctx, dxout, dy):
-        xout, mean, rstd, gamma = ctx.saved_tensors
-        if dy is None:
-            dy = torch.zeros(xout.shape, dtype=torch.bfloat16, device=xout.device)
-        dx, ddelta, dg, db = _ln_bwd(xout, mean, rstd, gamma, dy, dxout, True, ctx.sinks, ctx.drop)
-        return dx, ddelta.to(ctx.delta_dtype), _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None, None
-
-
-class _AddLayerNormScaled(torch.autograd.Function):
-    """x + delta * layerscale[c] * rowscale[sample] and its LayerNorm (CaiT blocks)."""
-
-    @staticmethod
-    def forward(ctx, x, delta, gamma, beta, ls, rowscale, rpb, eps):
-        lib = L.load()
-        C = x.shape[-1]
-        M = x.numel() // C
-        x, gamma, beta = _f32c(x, "x"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
-        delta_dtype = delta.dtype
-        delta = _bf16c(delta)
-        # the reference casts the LayerScale parameter to the compute dtype (layerscale.py:22): the
-        # kernels round the fp32 parameter to bf16 as they load it (no cast launches here)
-        lsf = _f32c(ls.detach(), "layerscale")
-        y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        xout = torch.empty_like(x)
-        L.check(lib.sae_layernorm_fwd_scaled(_stream(x), M, C, _ptr(x), _ptr(delta), _ptr(xout), _ptr(gamma),
-                                             _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), float(eps), _ptr(lsf),
-                                             _ptr(rowscale), int(rpb)))
-        ctx.save_for_backward(xout, mean, rstd, gamma, delta, lsf, rowscale)
-        ctx.rpb, ctx.delta_dtype, ctx.ls_dtype = int(rpb), delta_dtype, ls.dtype
-        ctx.sinks = (_sink(gamma), _sink(beta), _sink(ls) if ls.dtype == torch.float32 else None)
-        return xout, y
+    def forward(ctx, x, delta, gamma, beta, ls, rowscale, eps, drop, cls, stream):
+        ctx.full_shape, ctx.rows = (x.shape, (0, x.shape[1])) if cls else (None, (0, 1))
+        ctx.delta_dtype, ctx.ls_dtype = (None if t is None else t.dtype for t in (delta, ls))
+        scaled = None
+        if ls is not None:
+            # the reference casts the LayerScale parameter to the compute dtype (layerscale.py:22): the
+            # kernels round the fp32 parameter to bf16 as they load it (no cast launches here)
+            scaled = _LnScale(_f32c(ls.detach()), rowscale, x.shape[1])
+        xin, din = (x[:, 0], delta[:, 0]) if cls else (x, delta)
+        if din is not None:
+            din = _bf16c(din)
+        xout, y, mean, rstd = _ln_fwd(xin, din, gamma, beta, eps, drop, ctx.rows, scaled)
+        xs = xin if din is None else xout
+        ctx.save_for_backward(xs, mean, rstd, gamma, *(() if scaled is None else (din, scaled.ls, rowscale)))
+        ctx.drop = drop
+        ctx.sinks = (_sink(gamma), _sink(beta), _sink(ls) if ctx.ls_dtype == torch.float32 else None)
+        return (xs if stream else None), y
 
     @staticmethod
     @_sinking
-    def backward(ctx, dxout, dy):
-        xout, mean, rstd, gamma, delta, lsf, rowscale = ctx.saved_tensors
-        lib = L.load()
-        C = xout.shape[-1]
-        M = xout.numel() // C
-        if dy is None:
-            dy = torch.zeros(xout.shape, dtype=torch.bfloat16, device=xout.device)
-        dy = _bf16c(dy)
-        gamma = _f32c(gamma, "gamma")
-        dxin = _f32c(dxout, "dxin") if dxout is not None else None
-        dx = torch.empty_like(xout)
-        ddelta = torch.empty(xout.shape, dtype=torch.bfloat16, device=xout.device)
-        sg, sbt, sls = ctx.sinks
-        dg = _grad_out(sg, (C,), xout.device)
-        db = _grad_out(sbt, (C,), xout.device)
-        dls = _grad_out(sls, (C,), xout.device)
-        ws = torch.empty(lib.sae_layernorm_bwd_workspace_bytes(M, C), dtype=torch.uint8, device=xout.device)
-        L.check(lib.sae_layernorm_bwd_scaled(_stream(xout), M, C, _ptr(xout), _ptr(mean), _ptr(rstd), _ptr(gamma),
-                                             _ptr(dy), _ptr(dxin), _ptr(dx), _ptr(ddelta), _ptr(dg), _ptr(db),
-                                             _ptr(ws), _ptr(delta), _ptr(lsf), _ptr(rowscale), ctx.rpb, _ptr(dls)))
-        return (dx, ddelta.to(ctx.delta_dtype), _unsunk(dg, sg), _unsunk(db, sbt),
-                None if sls is not None else dls.to(ctx.ls_dtype), None, None, None)
+    def backward(ctx, dstream, dy):
+        # autograd hands an unused tensor output's gradient over as zeros (y unused: dx = 0 * rstd +
+        # dstream) and None for the stream that was not returned
+        xs, mean, rstd, gamma, *rest = ctx.saved_tensors
+        sg, sb, sls = ctx.sinks
+        scaled = _LnScale(rest[1], rest[2], xs.shape[1], rest[0], sls) if rest else None
+        dx, ddelta, dg, db, dls = _ln_bwd(xs, mean, rstd, gamma, dy, dstream, ctx.delta_dtype is not None, (sg, sb),
+                                          ctx.drop, ctx.rows, scaled)
+        if ctx.full_shape is not None:
+            dx, ddelta = _cls_rows(dx, ctx.full_shape, dx.dtype), _cls_rows(ddelta, ctx.full_shape, ctx.delta_dtype)
+        if ddelta is not None:
+            ddelta = ddelta.to(ctx.delta_dtype)
+        if dls is not None:
+            dls = _unsunk(dls.to(ctx.ls_dtype), sls)
+        return dx, ddelta, _unsunk(dg, sg), _unsunk(db, sb), dls, None, None, None, None, None
+
+
+def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = LN_EPS) -> torch.Tensor:
+    """Flax ``nn.LayerNorm(dtype=bfloat16)`` of an fp32 residual stream: bf16 output (HIP kernel)."""
+    _require_gpu(x)
+    return _LayerNorm.apply(x, None, gamma, beta, None, None, eps, None, False, False)[1]
+
+
+def layer_norm_pass(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = LN_EPS):
+    """``(x, LayerNorm(x))``: the encoder's first LayerNorm, returning its input as the residual stream
+    (see _LayerNorm)."""
+    _require_gpu(x, gamma, beta)
+    return _LayerNorm.apply(x, None, gamma, beta, None, None, eps, None, False, True)
+
+
+def add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                   eps: float = LN_EPS, dropout=None):
+    """``x + delta`` (fp32 residual add, models/vit.py:24,31) and its LayerNorm in bf16, one kernel;
+    returns ``(x + delta, LN(x + delta))``.  ``dropout = (rate, DropoutRng)``: the hidden dropout of
+    the addend (the attention-output / FF-output dropout of vit.py:22,29) applied as it is added,
+    ``x + delta * keep / pk``."""
+    _require_gpu(x, delta)
+    return _LayerNorm.apply(x, delta, gamma, beta, None, None, eps, _draw(dropout), False, True)
 
 
 def add_layer_norm_scaled(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
@@ -1590,23 +1576,16 @@ def add_layer_norm_scaled(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Ten
     _require_gpu(x, delta)
     if rowscale is not None:
         rowscale = rowscale.float().contiguous()
-    return _AddLayerNormScaled.apply(x, delta, gamma, beta, layerscale, rowscale, x.shape[1], eps)
+    return _LayerNorm.apply(x, delta, gamma, beta, layerscale, rowscale, eps, None, False, True)
 
 
-def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = LN_EPS) -> torch.Tensor:
-    """Flax ``nn.LayerNorm(dtype=bfloat16)`` of an fp32 residual stream: bf16 output (HIP kernel)."""
-    _require_gpu(x)
-    return _LayerNorm.apply(x, gamma, beta, eps)
-
-
-def add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                   eps: float = LN_EPS, dropout=None):
-    """``x + delta`` (fp32 residual add, models/vit.py:24,31) and its LayerNorm in bf16, one kernel;
-    returns ``(x + delta, LN(x + delta))``.  ``dropout = (rate, DropoutRng)``: the hidden dropout of
-    the addend (the attention-output / FF-output dropout of vit.py:22,29) applied as it is added,
-    ``x + delta * keep / pk``."""
-    _require_gpu(x, delta)
-    return _AddLayerNorm.apply(x, delta, gamma, beta, eps, _draw(dropout))
+def cls_add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                       eps: float = LN_EPS, dropout=None) -> torch.Tensor:
+    """bf16 LayerNorm(x[:, 0] + delta[:, 0]) of the [B, N, E] residual stream: the encoder's final
+    residual add and LayerNorm on the class-token rows only (see _LayerNorm).  ``dropout``: as
+    :func:`add_layer_norm`, with the class rows' slice of the full tensor's mask."""
+    _require_gpu(x, delta, gamma, beta)
+    return _LayerNorm.apply(x, delta, gamma, beta, None, None, eps, _draw(dropout), True, False)[1]
 
 
 # ------------------------------------------------------------------------------ training loss
@@ -1736,7 +1715,7 @@ class _EncoderTokens(torch.autograd.Function):
         x = torch.empty((B, Lt + 1, E), dtype=torch.float32, device=tokens.device)
         if drop is not None:
             L.check(lib.sae_tokens_fwd_dropout(_stream(tokens), B, Lt, E, _ptr(tokens), _ptr(cls), _ptr(pos), _ptr(x),
-                                               drop[0], _ptr(drop[1]), drop[2]))
+                                               *_drop_args(drop)))
         else:
             L.check(lib.sae_tokens_fwd(_stream(tokens), B, Lt, E, _ptr(tokens), _ptr(cls), _ptr(pos), _ptr(x)))
         ctx.shape, ctx.drop = (B, Lt, E), drop
@@ -1749,14 +1728,14 @@ class _EncoderTokens(torch.autograd.Function):
     def backward(ctx, dx):
         lib = L.load()
         B, Lt, E = ctx.shape
-        dx = _f32c(dx, "dx")
+        dx = _f32c(dx)
         dtok = torch.empty((B, Lt, E), dtype=torch.bfloat16, device=dx.device)
         scls, spos = ctx.sinks
         dcls = _grad_out(scls, ctx.meta[0], dx.device)
         dpos = _grad_out(spos, ctx.meta[1], dx.device)
         if ctx.drop is not None:
             L.check(lib.sae_tokens_bwd_dropout(_stream(dx), B, Lt, E, _ptr(dx), _ptr(dtok), _ptr(dcls), _ptr(dpos),
-                                               ctx.drop[0], _ptr(ctx.drop[1]), ctx.drop[2]))
+                                               *_drop_args(ctx.drop)))
         else:
             L.check(lib.sae_tokens_bwd(_stream(dx), B, Lt, E, _ptr(dx), _ptr(dtok), _ptr(dcls), _ptr(dpos)))
         return dtok, _unsunk(dcls, scls), _unsunk(dpos, spos), None
@@ -1781,71 +1760,6 @@ def encoder_tokens(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, d
         raise ValueError("encoder_tokens: needs bf16 contiguous tokens [B, L, E] (E % 4 == 0) and fp32 "
                          "contiguous cls [E] / pos [L+1, E]")
     return _EncoderTokens.apply(tokens, cls, pos, _draw(dropout))
-
-
-class _LayerNormPass(torch.autograd.Function):
-    """(x, LN(x)): the encoder's first LayerNorm, returning its input as the residual stream so that
-    the backward adds the residual gradient in the LayerNorm backward kernel (dx = dxout + LN'^T dy)
-    instead of autograd summing the two paths in a separate pass."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        _, y, mean, rstd = _ln_fwd(x, None, gamma, beta, eps)
-        ctx.save_for_backward(x, mean, rstd, gamma)
-        ctx.sinks = (_sink(gamma), _sink(beta))
-        return x, y
-
-    @staticmethod
-    @_sinking
-    def backward(ctx, dxout, dy):
-        x, mean, rstd, gamma = ctx.saved_tensors
-        if dy is None:
-            dy = torch.zeros(x.shape, dtype=torch.bfloat16, device=x.device)
-        dx, _, dg, db = _ln_bwd(x, mean, rstd, gamma, dy, dxout, False, ctx.sinks)
-        return dx, _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None
-
-
-def layer_norm_pass(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = LN_EPS):
-    """(x, LayerNorm(x)) -- see _LayerNormPass."""
-    _require_gpu(x, gamma, beta)
-    return _LayerNormPass.apply(x, gamma, beta, eps)
-
-
-class _ClsAddLayerNorm(torch.autograd.Function):
-    """LayerNorm(x[:, 0] + delta[:, 0]) -> bf16 [B, E]: the encoder's final residual add and
-    LayerNorm on the class-token rows only (ViT's head reads token 0, vit.py:95; the LayerNorm is
-    row-wise, so those rows' values equal the full pass's).  The backward writes the class rows of
-    dx (fp32) and ddelta (bf16); the other rows take no gradient from here."""
-
-    @staticmethod
-    def forward(ctx, x, delta, gamma, beta, eps, drop=None):
-        # dropout: the class rows are rows b * N of the [B * N, E] tensor -- the full form's mask
-        ctx.rows = (0, x.shape[1])
-        xout, y, mean, rstd = _ln_fwd(x[:, 0], delta[:, 0], gamma, beta, eps, drop, ctx.rows)
-        ctx.save_for_backward(xout, mean, rstd, gamma)
-        ctx.meta, ctx.drop = (x.shape, delta.dtype), drop
-        ctx.sinks = (_sink(gamma), _sink(beta))
-        return y
-
-    @staticmethod
-    @_sinking
-    def backward(ctx, dy):
-        xout, mean, rstd, gamma = ctx.saved_tensors
-        shape, ddt = ctx.meta
-        dxc, ddc, dg, db = _ln_bwd(xout, mean, rstd, gamma, dy, None, True, ctx.sinks, ctx.drop, ctx.rows)
-        dx = torch.zeros(shape, dtype=torch.float32, device=dxc.device)
-        dx[:, 0] = dxc
-        dd = torch.zeros(shape, dtype=ddt, device=dxc.device)
-        dd[:, 0] = ddc
-        return dx, dd, _unsunk(dg, ctx.sinks[0]), _unsunk(db, ctx.sinks[1]), None, None
-
-
-def cls_add_layer_norm(x: torch.Tensor, delta: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                       eps: float = LN_EPS, dropout=None) -> torch.Tensor:
-    """bf16 LayerNorm(x[:, 0] + delta[:, 0]) of the [B, N, E] residual stream -- see _ClsAddLayerNorm.
-    ``dropout``: as :func:`add_layer_norm`, with the class rows' slice of the full tensor's mask."""
-    _require_gpu(x, delta, gamma, beta)
-    return _ClsAddLayerNorm.apply(x, delta, gamma, beta, eps, _draw(dropout))
 
 
 # ------------------------------------------------- CvT projection: depthwise 3x3 conv + BatchNorm
@@ -1953,5 +1867,5 @@ def dwconv_bn(x: torch.Tensor, w: torch.Tensor, gamma: torch.Tensor, beta: torch
         raise ValueError("dwconv_bn: run_mean / run_var must be contiguous fp32 buffers (they are updated in place)")
     x = x.to(dtype)
     x = x if x.is_contiguous() else x.contiguous()
-    return _DwConvBn.apply(x, _f32c(w, "w"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), run_mean, run_var, int(stride),
+    return _DwConvBn.apply(x, _f32c(w), _f32c(gamma), _f32c(beta), run_mean, run_var, int(stride),
                            float(momentum), float(eps), bool(training))
