@@ -466,6 +466,39 @@ int sae_dwconv_bn_bwd(void* stream, const sae_dwconv_desc* desc, const void* x, 
                       const float* gamma, const void* t, const float* mean, const float* rstd,
                       const void* dy, void* dx, float* dw, float* dgamma, float* dbeta, void* workspace);
 
+/* The CvT convolutional token embedding (models/cvt.py:19-35): a dense kernel x kernel convolution
+   with stride < kernel and Flax SAME padding (Ho = ceil(H / stride), total padding
+   max((Ho - 1) stride + kernel - H, 0), the smaller half in front), as a window matrix written once
+   and the GEMMs above on it (forward P W on sae_gemm_nt / sae_gemm_f32, weight gradient P^T dY on
+   sae_gemm_dw / sae_gemm_f32, input gradient the scatter of dY W^T).
+     M = batch Ho Wo rows, K = kernel^2 channels columns, Kp = K rounded up to a multiple of 8
+     (sae_conv_window_cols); column (ky kernel + kx) channels + c, the Flax kernel [kh, kw, in, out]
+     viewed as [K, out].
+   sae_conv_window_gather:  P[m][col] = x[b][oy stride - pad_top + ky][ox stride - pad_left + kx][c],
+     zero for taps outside the image and for the columns K .. Kp.  x [B][H][W][channels] contiguous
+     in in_dtype, P [M][Kp] contiguous in dtype (the compute dtype): bf16 or fp32 x for a bf16 P
+     (fp32 values are rounded to nearest even as they are staged), fp32 x for an fp32 P.
+   sae_conv_window_scatter: dX[b][iy][ix][c] = the sum of dP[m(b, oy, ox)][(ky kernel + kx) channels + c]
+     over the windows with oy stride + ky = iy + pad_top, 0 <= oy < Ho (the same in x), in fp32,
+     ky ascending then kx ascending; dP [M][Kp] and dX [B][H][W][channels] in dtype.  A gather over
+     at most ceil(kernel / stride)^2 windows per pixel: no atomics, two calls agree bit for bit.
+   16-byte chunks where channels % 8 == 0 (bf16 P / dP) or % 4 == 0 (fp32), element accesses
+   otherwise; P, dP and (on the chunk path) x, dX must be 16-byte aligned.  Refused before any
+   launch: kernel outside 1..7, stride < 1, an extent < 1, an unknown dtype or a bf16 x with an fp32
+   P, NULL pointers, and extents whose element offsets (B H W channels, M Kp) exceed 2^31 - 1.
+   No workspace; graph-capturable. */
+typedef struct sae_convtok_desc {
+  int32_t batch, height, width, channels;
+  int32_t kernel;    /* 1..7 */
+  int32_t stride;    /* >= 1 */
+  int32_t in_dtype;  /* SAE_DTYPE_* of x (gather only) */
+  int32_t dtype;     /* SAE_DTYPE_* of P, dP and dX: the compute dtype */
+} sae_convtok_desc;
+/* Kp of a descriptor's window matrix, 0 for channels < 1 or kernel outside 1..7. */
+int32_t sae_conv_window_cols(int32_t channels, int32_t kernel);
+int sae_conv_window_gather(void* stream, const sae_convtok_desc* desc, const void* x, void* P);
+int sae_conv_window_scatter(void* stream, const sae_convtok_desc* desc, const void* dP, void* dX);
+
 /* Optimizer update of the data-parallel training step (train.py:25-27,229-233: optax.adamw,
    survey D9 descent), every parameter in ONE launch.  The parameters are cut into chunks of
    SAE_ADAMW_CHUNK elements; sae_adamw_plan (host only, no GPU call) fills that chunk table for

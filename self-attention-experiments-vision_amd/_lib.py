@@ -57,8 +57,17 @@ class SaeDwconvDesc(ctypes.Structure):
                 ("dtype", _i32), ("training", _i32), ("momentum", _f32), ("eps", _f32)]
 
 
+class SaeConvtokDesc(ctypes.Structure):
+    """Mirror of ``sae_convtok_desc`` (include/sae_attn.h)."""
+    _fields_ = [("batch", _i32), ("height", _i32), ("width", _i32), ("channels", _i32), ("kernel", _i32),
+                ("stride", _i32), ("in_dtype", _i32), ("dtype", _i32)]
+
+
 # (name, restype, argtypes) for every entry point declared in include/sae_attn.h
 _PROTOS = [
+    ("sae_conv_window_cols", _i32, [_i32, _i32]),
+    ("sae_conv_window_gather", _i32, [_vp, ctypes.POINTER(SaeConvtokDesc), _vp, _vp]),
+    ("sae_conv_window_scatter", _i32, [_vp, ctypes.POINTER(SaeConvtokDesc), _vp, _vp]),
     ("sae_dwconv_bn_workspace_bytes", _sz, [_i32] * 5),
     ("sae_dwconv_bn_fwd", _i32, [_vp, ctypes.POINTER(SaeDwconvDesc)] + [_vp] * 11),
     ("sae_dwconv_bn_bwd", _i32, [_vp, ctypes.POINTER(SaeDwconvDesc)] + [_vp] * 12),

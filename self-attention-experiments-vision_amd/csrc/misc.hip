@@ -2,10 +2,11 @@
 // (tokens.h), the hidden-state dropout of row-major activations (drop_rows.h: their dropout forms
 // and the standalone kernels), the cross-entropy family (label-smoothed, mixup / cutmix targets, top-k)
 // and the evaluation accumulator (loss.h), AdamW (adamw.h), the CvT convolutional projection
-// (depthwise 3x3 + BatchNorm, dwconv.h), the stream utilities of bench.py, and the library's error
-// string and version.
+// (depthwise 3x3 + BatchNorm, dwconv.h), the CvT convolutional token embedding's window matrix
+// (convtok.h), the stream utilities of bench.py, and the library's error string and version.
 #include "ln.h"
 #include "dwconv.h"
+#include "convtok.h"
 #include "loss.h"
 #include "tokens.h"
 #include "adamw.h"
@@ -373,6 +374,58 @@ int dw_bwd_launch(hipStream_t st, const sae_dwconv_desc& d, DwConvArgs& a) {
   return launch("dwconv_dx", fx[d.stride == 1 ? 0 : 1 + a.pl], gx, dim3(256), 0, st, a);
 }
 
+
+// ------------------------------------------- window matrix of the conv token embedding (CvT)
+// Everything but the pointers, and the geometry of convtok.h; every refusal returns before any HIP
+// call.  `gather`: in_dtype is read (the scatter has no x).
+int ct_geometry(const char* what, const sae_convtok_desc* d, bool gather, ConvTokGeom& g) {
+  if (!d) return fail(SAE_EINVAL, "%s: NULL descriptor", what);
+  if (d->kernel < 1 || d->kernel > 7) return fail(SAE_EUNSUPPORTED, "%s: kernel %d (1..7)", what, d->kernel);
+  if (d->stride < 1) return fail(SAE_EINVAL, "%s: stride %d must be >= 1", what, d->stride);
+  if (d->batch < 1 || d->height < 1 || d->width < 1 || d->channels < 1)
+    return fail(SAE_EINVAL, "%s: batch %d, height %d, width %d, channels %d must be >= 1", what, d->batch, d->height,
+                d->width, d->channels);
+  if (d->dtype != SAE_DTYPE_BF16 && d->dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "%s: bad dtype %d", what, d->dtype);
+  if (gather && d->in_dtype != SAE_DTYPE_BF16 && d->in_dtype != SAE_DTYPE_F32)
+    return fail(SAE_EINVAL, "%s: bad in_dtype %d", what, d->in_dtype);
+  if (gather && d->in_dtype == SAE_DTYPE_BF16 && d->dtype == SAE_DTYPE_F32)
+    return fail(SAE_EUNSUPPORTED, "%s: a bf16 x with an fp32 window matrix", what);
+  const int k = d->kernel, s = d->stride;
+  const long long Ho = ((long long)d->height + s - 1) / s, Wo = ((long long)d->width + s - 1) / s;
+  const long long K = (long long)k * k * d->channels, Kp = (K + 7) / 8 * 8, M = d->batch * Ho * Wo;
+  if ((long long)d->batch * d->height * d->width * d->channels > 0x7fffffffLL || M * Kp > 0x7fffffffLL)
+    return fail(SAE_EUNSUPPORTED, "%s: element offsets exceed 2^31 - 1 (x %lld, window matrix %lld elements)", what,
+                (long long)d->batch * d->height * d->width * d->channels, M * Kp);
+  const int N = d->dtype == SAE_DTYPE_BF16 ? 8 : 4;
+  g.B = d->batch;
+  g.H = d->height;
+  g.W = d->width;
+  g.C = d->channels;
+  g.k = k;
+  g.s = s;
+  g.Ho = (int)Ho;
+  g.Wo = (int)Wo;
+  g.pt = (int)std::max<long long>((Ho - 1) * s + k - g.H, 0) / 2;   // Flax SAME: the smaller half in front
+  g.pl = (int)std::max<long long>((Wo - 1) * s + k - g.W, 0) / 2;
+  g.K = (int)K;
+  g.Kp = (int)Kp;
+  g.M = (int)M;
+  g.nch = g.Kp / N;
+  g.total = g.M * g.nch;
+  g.cch = (g.C + N - 1) / N;
+  g.total_s = g.B * g.H * g.W * g.cch;   // (<= B H W C)
+  g.dnch = FDiv::make((unsigned)g.nch);
+  g.dHoWo = FDiv::make((unsigned)(g.Ho * g.Wo));
+  g.dWo = FDiv::make((unsigned)g.Wo);
+  g.dC = FDiv::make((unsigned)g.C);
+  g.dk = FDiv::make((unsigned)k);
+  g.dcch = FDiv::make((unsigned)g.cch);
+  g.dHW = FDiv::make((unsigned)(g.H * g.W));
+  g.dW = FDiv::make((unsigned)g.W);
+  g.ds = FDiv::make((unsigned)s);
+  return SAE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -630,6 +683,53 @@ int sae_dwconv_bn_bwd(void* stream, const sae_dwconv_desc* desc, const void* x, 
     return dw_bwd_launch<std::remove_pointer_t<decltype(p)>>((hipStream_t)stream, *desc, a);
   });
 }
+
+// ------------------------------------------- window matrix of the conv token embedding (CvT)
+int32_t sae_conv_window_cols(int32_t channels, int32_t kernel) {
+  if (channels < 1 || kernel < 1 || kernel > 7) return 0;
+  const long long Kp = ((long long)kernel * kernel * channels + 7) / 8 * 8;
+  return Kp > 0x7fffffffLL ? 0 : (int32_t)Kp;
+}
+
+int sae_conv_window_gather(void* stream, const sae_convtok_desc* desc, const void* x, void* P) {
+  ConvTokGeom g;
+  if (int rc = ct_geometry("conv_window_gather", desc, true, g)) return rc;
+  if (!x || !P) return fail(SAE_EINVAL, "conv_window_gather: NULL x / P");
+  const bool bf = desc->dtype == SAE_DTYPE_BF16, xbf = desc->in_dtype == SAE_DTYPE_BF16;
+  const bool vec = g.C % (bf ? 8 : 4) == 0;
+  if (!aligned16(P) || (vec && !aligned16(x)) || ((uintptr_t)x & (xbf ? 1 : 3)))
+    return fail(SAE_EINVAL, "conv_window_gather: P (and x on the 16-byte path) needs 16-byte alignment");
+  const long long grid = ((long long)g.total + 255) / 256;
+  hipStream_t st = (hipStream_t)stream;
+  if (!bf)
+    return launch("conv_window_gather", vec ? conv_window_gather_kernel<float, float, true>
+                                            : conv_window_gather_kernel<float, float, false>,
+                  grid, dim3(256), 0, st, g, reinterpret_cast<const float*>(x), reinterpret_cast<float*>(P));
+  if (xbf)
+    return launch("conv_window_gather", vec ? conv_window_gather_kernel<__bf16, __bf16, true>
+                                            : conv_window_gather_kernel<__bf16, __bf16, false>,
+                  grid, dim3(256), 0, st, g, reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(P));
+  return launch("conv_window_gather", vec ? conv_window_gather_kernel<float, __bf16, true>
+                                          : conv_window_gather_kernel<float, __bf16, false>,
+                grid, dim3(256), 0, st, g, reinterpret_cast<const float*>(x), reinterpret_cast<__bf16*>(P));
+}
+
+int sae_conv_window_scatter(void* stream, const sae_convtok_desc* desc, const void* dP, void* dX) {
+  ConvTokGeom g;
+  if (int rc = ct_geometry("conv_window_scatter", desc, false, g)) return rc;
+  if (!dP || !dX) return fail(SAE_EINVAL, "conv_window_scatter: NULL dP / dX");
+  const bool bf = desc->dtype == SAE_DTYPE_BF16;
+  const bool vec = g.C % (bf ? 8 : 4) == 0;
+  if (!aligned16(dP) || (vec && !aligned16(dX)) || ((uintptr_t)dX & (bf ? 1 : 3)))
+    return fail(SAE_EINVAL, "conv_window_scatter: dP (and dX on the 16-byte path) needs 16-byte alignment");
+  const long long grid = ((long long)g.total_s + 255) / 256;
+  return by_dtype(desc->dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return launch("conv_window_scatter", vec ? conv_window_scatter_kernel<T, true> : conv_window_scatter_kernel<T, false>,
+                  grid, dim3(256), 0, (hipStream_t)stream, g, reinterpret_cast<const T*>(dP), reinterpret_cast<T*>(dX));
+  });
+}
+
 
 // ---------------------------------------------------------------------------------- AdamW
 static_assert(sizeof(sae_adamw_chunk) == sizeof(AdamwChunk) && SAE_ADAMW_CHUNK == kAdamwChunk,

@@ -30,7 +30,8 @@ __all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "wei
            "add_layer_norm_scaled", "layer_norm_ok", "talking_heads_attention", "talking_heads_attention_packed",
            "relpos_bias", "rotary", "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer",
            "DenseFacts", "dense_facts_of_shapes", "dense_fwd_plan", "dense_bwd_plan",
-           "dwconv_bn", "dwconv_bn_ok", "same_pads"]
+           "dwconv_bn", "dwconv_bn_ok", "same_pads", "conv_tokens", "conv_tokens_ok", "conv_window_matrix",
+           "conv_window_scatter", "conv_window_cols"]
 
 
 class KernelTimer:
@@ -1869,3 +1870,164 @@ def dwconv_bn(x: torch.Tensor, w: torch.Tensor, gamma: torch.Tensor, beta: torch
     x = x if x.is_contiguous() else x.contiguous()
     return _DwConvBn.apply(x, _f32c(w), _f32c(gamma), _f32c(beta), run_mean, run_var, int(stride),
                            float(momentum), float(eps), bool(training))
+
+
+# --------------------------------------------- CvT token embedding: k x k convolution, stride < k
+def _convtok_desc(shape, kernel_size: int, stride: int, in_dtype: torch.dtype, dtype: torch.dtype) -> L.SaeConvtokDesc:
+    B, H, W, C = shape
+    return L.SaeConvtokDesc(int(B), int(H), int(W), int(C), int(kernel_size), int(stride), dtype_code(in_dtype),
+                            dtype_code(dtype))
+
+
+def conv_window_cols(channels: int, kernel_size: int) -> int:
+    """Columns of the window matrix: ``kernel_size^2 * channels`` rounded up to a multiple of 8."""
+    return -(-(kernel_size * kernel_size * channels) // 8) * 8
+
+
+def conv_window_matrix(x: torch.Tensor, kernel_size: int, stride: int, dtype: torch.dtype) -> torch.Tensor:
+    """The window matrix ``P`` [B * Ho * Wo, Kp] of ``x`` [B, H, W, Cin] (bf16 or fp32, contiguous) in
+    the compute dtype ``dtype`` (``sae_conv_window_gather``): row (b, oy, ox), column
+    ``(ky * k + kx) * Cin + c`` holds ``x[b, oy * s - pad_top + ky, ox * s - pad_left + kx, c]`` with the
+    Flax SAME pads of :func:`same_pads`; taps outside the image and the columns past ``k * k * Cin``
+    are zero.  fp32 values are rounded to bf16 as they are staged."""
+    lib = L.load()
+    _require_gpu(x)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("conv_window_matrix: x must be a contiguous [B, H, W, Cin] tensor")
+    d = _convtok_desc(x.shape, kernel_size, stride, x.dtype, dtype)
+    B, H, W, C = x.shape
+    M = B * -(-H // stride) * -(-W // stride)
+    P = torch.empty((M, conv_window_cols(C, kernel_size)), dtype=dtype, device=x.device)
+    tok = _TIMER.begin("conv_window_gather") if _TIMER is not None else None
+    L.check(lib.sae_conv_window_gather(_stream(x), ctypes.byref(d), _ptr(x), _ptr(P)))
+    if tok is not None:
+        _TIMER.end(tok, (M, P.shape[1]))
+    return P
+
+
+def conv_window_scatter(dP: torch.Tensor, x_shape, kernel_size: int, stride: int) -> torch.Tensor:
+    """The transpose of :func:`conv_window_matrix` (``sae_conv_window_scatter``): ``dX`` [B, H, W, Cin]
+    in ``dP``'s dtype, each element the fp32 sum, in a fixed order, of the entries of ``dP``
+    [B * Ho * Wo, Kp] that read it.  No atomics: two calls give the same bits."""
+    lib = L.load()
+    _require_gpu(dP)
+    B, H, W, C = (int(n) for n in x_shape)
+    M = B * -(-H // stride) * -(-W // stride)
+    if tuple(dP.shape) != (M, conv_window_cols(C, kernel_size)) or not dP.is_contiguous():
+        raise ValueError(f"conv_window_scatter: dP must be contiguous [{M}, {conv_window_cols(C, kernel_size)}], "
+                         f"got {tuple(dP.shape)}")
+    d = _convtok_desc((B, H, W, C), kernel_size, stride, dP.dtype, dP.dtype)
+    dX = torch.empty((B, H, W, C), dtype=dP.dtype, device=dP.device)
+    tok = _TIMER.begin("conv_window_scatter") if _TIMER is not None else None
+    L.check(lib.sae_conv_window_scatter(_stream(dP), ctypes.byref(d), _ptr(dP), _ptr(dX)))
+    if tok is not None:
+        _TIMER.end(tok, (B, H, W, C))
+    return dX
+
+
+def conv_tokens_ok(x, w, kernel_size: int, stride: int, dtype: torch.dtype) -> bool:
+    """Host predicate of :func:`conv_tokens`: a contiguous, 16-byte-aligned GPU tensor [B, H, W, Cin]
+    (bf16 or fp32), the Flax kernel [k, k, Cin, E] with k <= 7 and E % 8 == 0, stride >= 1, compute
+    dtype bf16 or fp32, and extents whose element offsets fit 31 bits."""
+    if not getattr(x, "is_cuda", False) or x.dim() != 4 or min(x.shape) < 1:
+        return False
+    if dtype not in (torch.bfloat16, torch.float32) or x.dtype not in (torch.bfloat16, torch.float32):
+        return False
+    k, s = int(kernel_size), int(stride)
+    B, H, W, C = x.shape
+    if not 1 <= k <= 7 or s < 1 or tuple(w.shape[:3]) != (k, k, C) or w.dim() != 4 or w.shape[3] % 8:
+        return False
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        return False
+    M = B * -(-H // s) * -(-W // s)
+    return x.numel() < 2 ** 31 and M * conv_window_cols(C, k) < 2 ** 31
+
+
+class _ConvTokens(torch.autograd.Function):
+    """models/cvt.py:28-33 as GEMMs on the window matrix P (``sae_conv_window_gather``): y = P W + b on
+    ``sae_gemm_nt`` (bf16) or ``sae_gemm_f32``; dW = P^T dY and db on ``sae_gemm_dw`` / ``sae_gemm_f32``
+    (into their gradient sinks inside a sink window); for an input that takes a gradient, and only
+    then, dP = dY W^T on the same GEMMs and ``sae_conv_window_scatter``.  P is saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, k, s, dt):
+        K, E = k * k * x.shape[3], w.shape[3]
+        B, H, W, _ = x.shape
+        L_out = -(-H // s) * -(-W // s)
+        tok = _TIMER.begin("conv_tokens_fwd") if _TIMER is not None else None
+        P = conv_window_matrix(x, k, s, dt)
+        Kp = P.shape[1]
+        w2 = w.detach().reshape(K, E)
+        if w2.dtype != torch.float32 or not w2.is_contiguous():
+            w2 = w2.float().contiguous()
+        if Kp != K:   # zero rows for the pad columns of P
+            w2 = torch.nn.functional.pad(w2, (0, 0, 0, Kp - K))
+        bias = b.detach().float().contiguous() if b is not None else None
+        if dt == torch.bfloat16:
+            wk, wt = weight_cast(w2)          # [Kp, E] for dP, [E, Kp] for the forward
+            y = gemm_nt(P, wt, bias)
+        else:
+            wk = w2
+            y = gemm_f32(P, wk, bias)
+        if tok is not None:
+            _TIMER.end(tok, (B * L_out, K, E))
+        ctx.save_for_backward(P, wk)
+        ctx.geom = (tuple(x.shape), k, s, K, E)
+        ctx.wshape, ctx.wdtype, ctx.has_b, ctx.xdtype = tuple(w.shape), w.dtype, b is not None, x.dtype
+        ctx.sinks = (_sink(w), _sink(b))
+        return y.view(B, L_out, E)
+
+    @staticmethod
+    @_sinking
+    def backward(ctx, dy):
+        P, wk = ctx.saved_tensors
+        xshape, k, s, K, E = ctx.geom
+        Kp, dt, dev = P.shape[1], P.dtype, P.device
+        dy2 = dy.to(dt).reshape(-1, E)
+        if not dy2.is_contiguous() or dy2.data_ptr() % 16:
+            dy2 = dy2.contiguous()
+        sw, sb = ctx.sinks   # flat-buffer sinks (the training step): written in place
+        tok = _TIMER.begin("conv_tokens_bwd") if _TIMER is not None else None
+        db = _grad_out(sb, (E,), dev) if ctx.has_b else None
+        # K == Kp: the kernel's gradient (or its sink) is the GEMM's output; else the first K rows of it
+        direct = Kp == K
+        dwp = _grad_out(sw.view(K, E) if sw is not None else None, (K, E), dev) if direct else \
+            torch.empty((Kp, E), dtype=torch.float32, device=dev)
+        if dt == torch.bfloat16:
+            gemm_dw(P, dy2, dwp, db)
+        else:
+            gemm_f32(P.t(), dy2, out=dwp, colsum=db)
+        if direct:
+            dw = None if sw is not None else dwp.view(ctx.wshape).to(ctx.wdtype)
+        elif sw is not None:
+            _claim(sw).view(K, E).copy_(dwp[:K])
+            dw = None
+        else:
+            dw = dwp[:K].reshape(ctx.wshape).to(ctx.wdtype)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            tok2 = _TIMER.begin("conv_tokens_dp") if _TIMER is not None else None
+            dP = gemm_nt(dy2, wk) if dt == torch.bfloat16 else gemm_f32(dy2, wk.t())
+            if tok2 is not None:
+                _TIMER.end(tok2, (dy2.shape[0], E, Kp))
+            dx = conv_window_scatter(dP, xshape, k, s).to(ctx.xdtype)
+        if tok is not None:
+            _TIMER.end(tok, (dy2.shape[0], K, E))
+        return dx, dw, _unsunk(db, sb), None, None, None
+
+
+def conv_tokens(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], kernel_size: int, stride: int,
+                dtype: torch.dtype) -> torch.Tensor:
+    """The convolution of ``ConvTokenEmbedBlock`` (models/cvt.py:28-33): ``x`` [B, H, W, Cin] (bf16 or
+    fp32) with the Flax kernel ``w`` [k, k, Cin, E] (+ ``b``), stride ``stride``, SAME padding, in the
+    compute dtype ``dtype`` -> tokens [B, Ho * Wo, E].  Gradients of w and b always, of x only when it
+    requires one (the first stage's input is the image batch).  See :func:`conv_tokens_ok`."""
+    _require_gpu(x, w)
+    if x.dtype not in (torch.bfloat16, torch.float32) or (x.dtype == torch.bfloat16 and dtype == torch.float32):
+        x = x.to(dtype)
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        x = x.contiguous()
+    if not conv_tokens_ok(x, w, kernel_size, stride, dtype):
+        raise ValueError(f"conv_tokens: unsupported call (x {tuple(x.shape)}, kernel {tuple(w.shape)}, stride {stride}, "
+                         f"{dtype}); see conv_tokens_ok")
+    return _ConvTokens.apply(x, w, b, int(kernel_size), int(stride), dtype)

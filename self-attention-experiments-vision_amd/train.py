@@ -837,6 +837,10 @@ class TrainStep:
         train.py:94-100)."""
         dev = self._images.device
         snap = [p.detach().clone() for p in self._params]
+        # buffers a training forward advances (the BatchNorm running statistics of a CvT; none in the
+        # other models): put back too, so the first call moves them once
+        bufs = list(self.model.buffers())
+        snap_buf = [t.detach().clone() for t in bufs]
         snap_opt = self._opt_snapshot()
         snap_rng = self._drop_rng.state.clone() if self._drop_rng is not None else None
         s = torch.cuda.Stream(device=dev)
@@ -849,6 +853,8 @@ class TrainStep:
         with torch.no_grad():
             for p, v in zip(self._params, snap):
                 p.copy_(v)
+            for t, v in zip(bufs, snap_buf):
+                t.copy_(v)
             if snap_rng is not None:   # the warm-up steps advanced the dropout offset
                 self._drop_rng.state.copy_(snap_rng)
             self._opt_restore(snap_opt)
