@@ -11,9 +11,12 @@ Numerics: fp32 params, ``dtype`` compute, fp32 residual stream.  Survey D7: the 
 not pass ``dtype`` to the self-attention trunk (cait.py:147-154), so its trunk runs in fp32 even
 for a bf16 model; this build runs the trunk in the model's ``dtype`` (the bf16 config of
 BASELINE) -- ``trunk_dtype=torch.float32`` restores the reference behaviour.
-Hot path: every self-attention layer runs the fused talking-heads kernels
-(``ops.talking_heads_attention``), every class-attention layer the fused core with Nq = 1
-(CLS query), every FF block ``ops.ff_block`` (GELU fused into the GEMM epilogues).
+Every self-attention layer runs the fused talking-heads kernels (``ops.talking_heads_attention``), every class-attention
+layer the fused core with Nq = 1 (CLS query), every FF block ``ops.ff_block``.  The trunk block is written once,
+``EncoderBlock.body``, on the stream operations of ``layers/stream.py``: each add of a branch times LayerScale times
+the stochastic-depth factor is made together with the LayerNorm that follows it.  ``Encoder.forward`` decides the route
+once, on the stream that enters the first block: one ``ops.add_layer_norm_scaled`` kernel per add on the HIP route,
+framework ops on the other (an fp32 trunk).  A class-attention block decides per call, for its LayerNorms only.
 """
 from __future__ import annotations
 
@@ -22,9 +25,9 @@ from typing import Tuple
 import torch
 import torch.nn as nn
 
-from . import ops
-from .layers.attention import ClassSelfAttentionBlock, SelfAttentionBlock
-from .vit import Dense, FFBlock, LayerNorm, encoder_weight_groups, patch_tokens
+from .layers.attention import ClassSelfAttentionBlock, SelfAttentionBlock, numbered
+from .layers.stream import add_norm, fused, norm, scaled
+from .vit import Dense, FFBlock, LayerNorm, encoder_casts, encoder_weight_groups, patch_tokens
 
 __all__ = ["CaiT", "create_cait", "CAIT_CONFIGS", "cait_flops_per_image", "LayerScaleBlock",
            "StochasticDepthBlock"]
@@ -62,14 +65,9 @@ class StochasticDepthBlock(nn.Module):
 
 def scaled_branch(x: torch.Tensor, ls: LayerScaleBlock, sd: StochasticDepthBlock, dtype: torch.dtype,
                   is_training: bool) -> torch.Tensor:
-    """``StochasticDepth(LayerScale(x))`` as ONE elementwise pass: x * (layerscale[c] * mask[b] /
-    keep), the [B, 1, C] factor built first (same math as the two blocks applied in turn,
-    layerscale.py:21-23 then stochastic_depth.py:19-28, up to the bf16 rounding of the factor)."""
-    f = ls.layerscale.to(dtype)
-    rs = sample_scale(x.shape[0], sd, is_training, x.device)
-    if rs is not None:
-        f = f[None, None, :] * rs[:, None, None].to(dtype)
-    return x.to(dtype) * f
+    """``StochasticDepth(LayerScale(x))`` as one elementwise pass (``stream.scaled``): the two blocks applied
+    in turn, layerscale.py:21-23 then stochastic_depth.py:19-28, up to the bf16 rounding of the factor."""
+    return scaled(x, ls.layerscale, sample_scale(x.shape[0], sd, is_training, x.device), dtype)
 
 
 # the factors of every stochastic-depth block of one training forward, drawn together
@@ -118,18 +116,21 @@ class EncoderBlock(nn.Module):
         self.LayerScaleBlock_1 = LayerScaleBlock(dim, layerscale_eps, device)
         self.StochasticDepthBlock_1 = StochasticDepthBlock(stoch_depth_rate)
 
-    def _ln(self, ln, x):
-        if self.dtype == torch.bfloat16 and ops.layer_norm_ok(x):
-            return ops.layer_norm(x, ln.scale, ln.bias)
-        return ln(x, self.dtype)
+    def body(self, x, h, next_ln, is_training, route):
+        """The block on the stream ``x`` and ``h = LayerNorm_0(x)`` -> ``(x', next_ln(x'))`` (``stream.add_norm``)."""
+        ls0, ls1 = self.LayerScaleBlock_0.layerscale, self.LayerScaleBlock_1.layerscale
+        a = self.SelfAttentionBlock_0(h, is_training=is_training)
+        rs = sample_scale(x.shape[0], self.StochasticDepthBlock_0, is_training, x.device)
+        x, h = add_norm(x, a, self.LayerNorm_1, self.dtype, route, layerscale=ls0, rowscale=rs)
+        f = self.FFBlock_0(h, self.dtype)
+        rs = sample_scale(x.shape[0], self.StochasticDepthBlock_1, is_training, x.device)
+        return add_norm(x, f, next_ln, self.dtype, route, layerscale=ls1, rowscale=rs)
 
     def forward(self, inputs: torch.Tensor, is_training: bool) -> torch.Tensor:
-        x = self.SelfAttentionBlock_0(self._ln(self.LayerNorm_0, inputs), is_training=is_training)
-        x = scaled_branch(x, self.LayerScaleBlock_0, self.StochasticDepthBlock_0, self.dtype, is_training)
-        x = x + inputs                                         # fp32 residual stream
-        y = self.FFBlock_0(self._ln(self.LayerNorm_1, x), self.dtype)
-        y = scaled_branch(y, self.LayerScaleBlock_1, self.StochasticDepthBlock_1, self.dtype, is_training)
-        return x + y
+        """The body on the route of ``inputs``: a lone bf16 block now fuses its first add too, as in the encoder."""
+        route = fused(inputs, self.dtype)
+        h = norm(inputs, self.LayerNorm_0, self.dtype, route)
+        return self.body(inputs, h, None, is_training, route)[0]
 
 
 class Encoder(nn.Module):
@@ -138,6 +139,7 @@ class Encoder(nn.Module):
     def __init__(self, num_tokens, dim, num_layers, num_heads, stoch_depth_rate, layerscale_eps, expand_ratio,
                  dtype, device=None):
         super().__init__()
+        self.dtype = dtype
         self.AddAbsPosEmbed_0 = nn.Module()
         self.AddAbsPosEmbed_0.pos_embed = nn.Parameter(torch.randn(1, num_tokens, dim, device=device) * 0.02)
         self.num_layers = num_layers
@@ -147,32 +149,15 @@ class Encoder(nn.Module):
 
     def forward(self, inputs: torch.Tensor, is_training: bool) -> torch.Tensor:
         x = inputs.float() + self.AddAbsPosEmbed_0.pos_embed
-        blocks = [getattr(self, f"EncoderBlock_{i}") for i in range(self.num_layers)]
-        if blocks and blocks[0].dtype == torch.bfloat16 and ops.layer_norm_ok(x):
-            # cait.py:30-60 per block, every residual add fused with the LayerNorm that follows it
-            # (this block's LayerNorm_1, the next block's LayerNorm_0): one HBM pass each
-            with ops.forward_casts(encoder_weight_groups(blocks)):   # every Dense kernel, one launch
-                return self._fused(x, blocks, is_training)
-        for blk in blocks:
-            x = blk(x, is_training)
-        return x
-
-    @staticmethod
-    def _fused(x, blocks, is_training):
-        h = ops.layer_norm(x, blocks[0].LayerNorm_0.scale, blocks[0].LayerNorm_0.bias)
-        for i, blk in enumerate(blocks):
-            # LayerScale x stochastic depth folded into the residual add + LayerNorm kernel
-            a = blk.SelfAttentionBlock_0(h, is_training=is_training)
-            rs = sample_scale(x.shape[0], blk.StochasticDepthBlock_0, is_training, x.device)
-            x, h = ops.add_layer_norm_scaled(x, a, blk.LayerNorm_1.scale, blk.LayerNorm_1.bias,
-                                             blk.LayerScaleBlock_0.layerscale, rs)
-            f = blk.FFBlock_0(h, blk.dtype)
-            if i + 1 < len(blocks):
-                nxt = blocks[i + 1].LayerNorm_0
-                rs = sample_scale(x.shape[0], blk.StochasticDepthBlock_1, is_training, x.device)
-                x, h = ops.add_layer_norm_scaled(x, f, nxt.scale, nxt.bias, blk.LayerScaleBlock_1.layerscale, rs)
-            else:
-                x = x + scaled_branch(f, blk.LayerScaleBlock_1, blk.StochasticDepthBlock_1, blk.dtype, is_training)
+        blocks = numbered(self, "EncoderBlock")
+        if not blocks:
+            return x
+        route = fused(x, self.dtype)   # decided here, on the stream that enters the first block, and held
+        lns = [blk.LayerNorm_0 for blk in blocks[1:]] + [None]   # what reads each block's output
+        with encoder_casts(blocks, route):
+            h = norm(x, blocks[0].LayerNorm_0, self.dtype, route)
+            for blk, ln in zip(blocks, lns):
+                x, h = blk.body(x, h, ln, is_training, route)
         return x
 
 
@@ -192,17 +177,14 @@ class CAEncoderBlock(nn.Module):
         self.LayerScaleBlock_1 = LayerScaleBlock(dim, layerscale_eps, device)
         self.StochasticDepthBlock_1 = StochasticDepthBlock(stoch_depth_rate)
 
-    def _ln(self, ln, x):
-        if self.dtype == torch.bfloat16 and ops.layer_norm_ok(x):
-            return ops.layer_norm(x, ln.scale, ln.bias)
-        return ln(x, self.dtype)
-
     def forward(self, inputs: torch.Tensor, cls_token: torch.Tensor, is_training: bool) -> torch.Tensor:
-        x = torch.cat([cls_token, inputs], dim=1)
-        x = self.ClassSelfAttentionBlock_0(self._ln(self.LayerNorm_0, x.contiguous()), is_training=is_training)
+        x = torch.cat([cls_token, inputs], dim=1).contiguous()
+        x = norm(x, self.LayerNorm_0, self.dtype, fused(x, self.dtype))      # decided per call, per stream
+        x = self.ClassSelfAttentionBlock_0(x, is_training=is_training)
         x = scaled_branch(x, self.LayerScaleBlock_0, self.StochasticDepthBlock_0, self.dtype, is_training)
         cls_token = cls_token + x
-        y = self.FFBlock_0(self._ln(self.LayerNorm_1, cls_token.contiguous()), self.dtype)
+        c = cls_token.contiguous()
+        y = self.FFBlock_0(norm(c, self.LayerNorm_1, self.dtype, fused(c, self.dtype)), self.dtype)
         y = scaled_branch(y, self.LayerScaleBlock_1, self.StochasticDepthBlock_1, self.dtype, is_training)
         return cls_token + y
 
@@ -235,13 +217,11 @@ class CaiT(nn.Module):
         the trunk's column-block groups (when the trunk computes in bf16), the patch embedding and
         the head and the class-attention blocks' projections / FF (when the model does)."""
         groups = []
-        blocks = [getattr(self.Encoder_0, f"EncoderBlock_{i}") for i in range(self.Encoder_0.num_layers)]
-        if blocks and blocks[0].dtype == torch.bfloat16:
-            groups += encoder_weight_groups(blocks)
+        if self.Encoder_0.dtype == torch.bfloat16:
+            groups += encoder_weight_groups(numbered(self.Encoder_0, "EncoderBlock"))
         if self.dtype == torch.bfloat16:
             groups += [[self.PatchEmbedBlock_0.Dense_0.kernel], [self.Dense_0.kernel]]
-            for i in range(self.num_layers_token_only):
-                ca = getattr(self, f"CAEncoderBlock_{i}")
+            for ca in numbered(self, "CAEncoderBlock"):
                 groups += ca.ClassSelfAttentionBlock_0.cross_weight_groups()
                 groups += [[ca.FFBlock_0.Dense_0.kernel], [ca.FFBlock_0.Dense_1.kernel]]
         return groups or None
@@ -268,8 +248,8 @@ class CaiT(nn.Module):
         try:
             x = self.Encoder_0(x, is_training)
             cls_token = self.cls.expand(b, 1, self.embed_dim).float()
-            for i in range(self.num_layers_token_only):
-                cls_token = getattr(self, f"CAEncoderBlock_{i}")(x, cls_token, is_training)
+            for ca in numbered(self, "CAEncoderBlock"):
+                cls_token = ca(x, cls_token, is_training)
         finally:
             _SD_DRAW = prev
         # LayerNorm over [cls, x] then take the CLS row: LN is per token, so normalising the CLS row

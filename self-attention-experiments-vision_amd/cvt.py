@@ -9,12 +9,13 @@ Class names, fields, call signatures and the Flax parameter tree are the referen
 ``Stage_{last}/cls``, ``Dense_0``; the BatchNorm ``mean`` / ``var`` of the convolutional projections are
 buffers (Flax ``batch_stats``).
 
-Hot path.  The stem's convolution is ``ops.conv_tokens`` (the window matrix written once by
-``sae_conv_window_gather``, then the project's GEMMs; the input gradient through
-``sae_conv_window_scatter``, for stages 2 and 3 only: the image batch takes none) and its LayerNorm
-``ops.layer_norm``; a stage block is ``zero_pad_and_reshape`` -> ``CvTSelfAttentionBlock`` -> residual
-add + LayerNorm in one kernel (``ops.add_layer_norm``) -> ``ops.ff_block`` -> residual add.  Calls
-outside ``ops.conv_tokens_ok`` keep the framework route, ``ConvTokenEmbedBlock._framework_forward``.
+The stem's convolution is ``ops.conv_tokens`` (the window matrix written once by ``sae_conv_window_gather``, then the
+project's GEMMs; the input gradient through ``sae_conv_window_scatter``, for stages 2 and 3 only: the image batch
+takes none); calls outside ``ops.conv_tokens_ok`` keep the framework route,
+``ConvTokenEmbedBlock._framework_forward``.  A stage block is ``zero_pad_and_reshape`` -> ``CvTSelfAttentionBlock``
+-> residual add + LayerNorm -> ``ops.ff_block`` -> residual add.  The stem and each stage block decide the route of
+their LayerNorm per call, on their own stream (``layers/stream.py``): ``ops.layer_norm`` and one
+``ops.add_layer_norm`` kernel on the HIP route, framework ops on the other.
 Numerics follow the other models here: fp32 parameters, ``dtype`` compute, fp32 residual stream.
 
 Behaviour of the reference that is kept as it is:
@@ -43,7 +44,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .layers.attention import numbered
 from .layers.cvt import CvTSelfAttentionBlock, _Conv
+from .layers.stream import add_norm, fused, norm
 from .vit import Dense, FFBlock, LayerNorm
 
 __all__ = ["zero_pad_and_reshape", "ConvTokenEmbedBlock", "StageBlock", "Stage", "CvT", "create_cvt",
@@ -81,13 +84,8 @@ class ConvTokenEmbedBlock(nn.Module):
         k, s, dt = self.kernel_size, self.strides, self.dtype
         if not ops.conv_tokens_ok(inputs, self.Conv_0.kernel, k, s, dt):
             return self._framework_forward(inputs)
-        y = ops.conv_tokens(inputs, self.Conv_0.kernel, self.Conv_0.bias, k, s, dt)
-        ln = self.LayerNorm_0
-        if dt == torch.bfloat16:
-            yf = y.float()
-            if ops.layer_norm_ok(yf):
-                return ops.layer_norm(yf, ln.scale, ln.bias)
-        return ln(y, dt)
+        y = ops.conv_tokens(inputs, self.Conv_0.kernel, self.Conv_0.bias, k, s, dt).float()
+        return norm(y, self.LayerNorm_0, dt, fused(y, dt))
 
     def _framework_conv(self, inputs: torch.Tensor) -> torch.Tensor:
         """The convolution as ``F.conv2d`` on explicitly SAME-padded input -> [b, Ho Wo, out] in dtype.
@@ -126,13 +124,9 @@ class StageBlock(nn.Module):
         grid = zero_pad_and_reshape(inputs)
         a = self.CvTSelfAttentionBlock_0(grid, is_training=is_training)
         res = grid.reshape(grid.shape[0], -1, grid.shape[3])
-        ln = self.LayerNorm_0
-        if self.dtype == torch.bfloat16 and ops.layer_norm_ok(res):
-            x, y = ops.add_layer_norm(res, a, ln.scale, ln.bias)   # the residual add and its LayerNorm, one kernel
-        else:
-            x = a + res
-            y = ln(x, self.dtype)
-        return x + self.FFBlock_0(y, self.dtype, is_training)
+        route = fused(res, self.dtype)
+        x, y = add_norm(res, a, self.LayerNorm_0, self.dtype, route)
+        return add_norm(x, self.FFBlock_0(y, self.dtype, is_training), None, self.dtype, route)[0]
 
 
 class Stage(nn.Module):
@@ -156,8 +150,8 @@ class Stage(nn.Module):
         x = self.ConvTokenEmbedBlock_0(inputs, is_training=is_training).float()   # the fp32 residual stream
         if self.insert_cls:
             x = torch.cat([self.cls.expand(x.shape[0], 1, self.embed_dim), x], dim=1)
-        for i in range(self.size):
-            x = getattr(self, f"StageBlock_{i}")(x, is_training=is_training)
+        for blk in numbered(self, "StageBlock"):
+            x = blk(x, is_training=is_training)
         return x
 
 
@@ -190,14 +184,14 @@ class CvT(nn.Module):
             inputs = inputs.permute(3, 0, 1, 2).contiguous()
         elif layout != "NHWC":
             raise ValueError(f"CvT: layout must be 'NHWC' or 'HWCN', got {layout!r}")
+        *stages, last = numbered(self, "Stage")
         x = inputs
-        n = len(self.stage_sizes)
-        for i in range(n - 1):
-            x = getattr(self, f"Stage_{i}")(x, is_training=is_training)
+        for stage in stages:
+            x = stage(x, is_training=is_training)
             b, l, c = x.shape
             S = math.isqrt(l)                     # 'b (H W) c -> b H W c', H = int(sqrt(l))
             x = x.reshape(b, S, l // S, c)
-        x = getattr(self, f"Stage_{n - 1}")(x, is_training=is_training)
+        x = last(x, is_training=is_training)
         return self.Dense_0(x[:, 0].contiguous(), self.dtype)
 
 

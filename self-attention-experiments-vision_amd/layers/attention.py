@@ -36,8 +36,8 @@ from .. import ops
 ROTARY_BASE = 10000.0
 
 __all__ = ["DenseGeneral", "AttentionBlock", "SelfAttentionBlock", "TalkingHeadsBlock",
-           "ClassSelfAttentionBlock", "LCSelfAttentionBlock", "lecun_normal_", "flax_params",
-           "load_flax_params"]
+           "ClassSelfAttentionBlock", "LCSelfAttentionBlock", "attention_tail", "lecun_normal_", "numbered",
+           "flax_params", "load_flax_params"]
 
 
 def lecun_normal_(t: torch.Tensor, fan_in: int) -> torch.Tensor:
@@ -76,6 +76,31 @@ class TalkingHeadsBlock(nn.Module):
         w = self.talking_heads_transform
         return torch.einsum("hi,bh...->bi...", w.to(torch.promote_types(w.dtype, inputs.dtype)),
                             inputs.to(torch.promote_types(w.dtype, inputs.dtype)))
+
+
+def attention_tail(blk, q, k, v, is_training: bool, qkv=None, rope=None) -> torch.Tensor:
+    """What follows the projections of ``blk`` (attention.py:39-67, cvt_attention.py:85-113): the core on q, k, v
+    [B, N, H, D] or on the packed ``qkv`` [B, N, 3, H, D] they are views of, the output projection, its dropout."""
+    drop = None   # attention-probability dropout (attention.py:54-58): inside the attention kernels
+    if is_training and blk.attn_dropout_rate > 0.0:
+        if blk.talking_heads:
+            raise NotImplementedError(
+                "attn_dropout_rate > 0 with talking_heads=True is not implemented: the reference drops after the "
+                "second head mix (attention.py:50-56, cvt_attention.py:100-104); the talking-heads kernels have none")
+        drop = (blk.attn_dropout_rate, ops.dropout_rng(q.device))
+    B, Nq, H, D = q.shape
+    scale = 1.0 / math.sqrt(D)
+    if blk.talking_heads:
+        th = (blk.TalkingHeadsBlock_0.talking_heads_transform, blk.TalkingHeadsBlock_1.talking_heads_transform)
+        o = (ops.talking_heads_attention_packed(qkv, *th, scale, rope) if qkv is not None else
+             ops.talking_heads_attention(q, k, v, *th, scale, rope))
+    elif qkv is not None:
+        o = ops.attention_packed(qkv, scale, rope, dropout=drop)
+    else:
+        o = ops.attention(q, k, v, scale, rotary=rope, dropout=drop)
+    out = blk.DenseGeneral_0
+    y = ops.dense(o.reshape(B, Nq, H * D), out.kernel.reshape(H * D, -1), out.bias if blk.use_bias else None, blk.dtype)
+    return F.dropout(y, p=blk.out_dropout_rate, training=is_training) if blk.out_dropout_rate > 0.0 else y
 
 
 class AttentionBlock(nn.Module):
@@ -141,54 +166,22 @@ class AttentionBlock(nn.Module):
             self._build(in_ch, inputs_q.device)
         elif self._in_ch != in_ch:
             raise ValueError(f"AttentionBlock built for {self._in_ch} channels, got {in_ch}")
-        # attention-probability dropout (attention.py:54-58): inside the attention kernels
-        drop = None
-        if is_training and self.attn_dropout_rate > 0.0:
-            if self.talking_heads:
-                raise NotImplementedError(
-                    "attn_dropout_rate > 0 with talking_heads=True is not implemented: the reference drops after "
-                    "the second head mix (attention.py:50-56), and the talking-heads kernels have no dropout")
-            drop = (self.attn_dropout_rate, ops.dropout_rng(inputs_q.device))
-        H, D = self.num_heads, self._head_ch_eff
-        dt = self.dtype
-        B, Nq, C = inputs_q.shape
-        Nk = inputs_kv.shape[1]
-        xq = inputs_q.to(dt)
-        scale = 1.0 / math.sqrt(D)
-        HD = H * D
-        wq, wk, wv = (m.kernel for m in (self.queries, self.keys, self.values))     # fp32 [C, H, D]
-        bias = (lambda *ms: torch.stack([m.bias for m in ms], 0).reshape(-1)) if self.use_bias else None
-        self_attn = inputs_q is inputs_kv
-        if self_attn:
+        H, D, dt = self.num_heads, self._head_ch_eff, self.dtype
+        B, Nq, _ = inputs_q.shape
+        xq, qkv = inputs_q.to(dt), None
+        bias = lambda *ms: torch.stack([m.bias for m in ms], 0).reshape(-1) if self.use_bias else None
+        if inputs_q is inputs_kv:
             # ONE projection GEMM producing the packed [B, N, 3, H, D] buffer the kernels read in place
-            w = [wq.reshape(C, HD), wk.reshape(C, HD), wv.reshape(C, HD)]   # = stack(dim=1) columns
-            qkv = ops.dense(xq, w, bias(self.queries, self.keys, self.values) if bias else None, dt)
+            qkv = ops.dense(xq, self.weight_groups()[0], bias(self.queries, self.keys, self.values), dt)
             qkv = qkv.view(B, Nq, 3, H, D)
             q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         else:
-            xkv = inputs_kv.to(dt)
-            q = ops.dense(xq, wq.reshape(C, HD), self.queries.bias.reshape(-1) if bias else None, dt)
-            q = q.view(B, Nq, H, D)
-            kv = ops.dense(xkv, [wk.reshape(C, HD), wv.reshape(C, HD)],
-                           bias(self.keys, self.values) if bias else None, dt).view(B, Nk, 2, H, D)
+            wq, wkv, _ = self.cross_weight_groups()
+            q = ops.dense(xq, wq, self.queries.bias.reshape(-1) if self.use_bias else None, dt).view(B, Nq, H, D)
+            kv = ops.dense(inputs_kv.to(dt), wkv, bias(self.keys, self.values), dt).view(B, -1, 2, H, D)
             k, v = kv[:, :, 0], kv[:, :, 1]
         # rotary (position_embed.py:8-20) rides inside the attention kernels: q / k stay un-rotated
-        rope = ROTARY_BASE if self.rotary else None
-        if self.talking_heads and self_attn:
-            o = ops.talking_heads_attention_packed(qkv, self.TalkingHeadsBlock_0.talking_heads_transform,
-                                                   self.TalkingHeadsBlock_1.talking_heads_transform, scale, rope)
-        elif self.talking_heads:
-            o = ops.talking_heads_attention(q, k, v, self.TalkingHeadsBlock_0.talking_heads_transform,
-                                            self.TalkingHeadsBlock_1.talking_heads_transform, scale, rope)
-        elif self_attn:
-            o = ops.attention_packed(qkv, scale, rope, dropout=drop)
-        else:
-            o = ops.attention(q, k, v, scale, rotary=rope, dropout=drop)
-        wo = self.DenseGeneral_0.kernel.reshape(HD, self._out_ch_eff)
-        y = ops.dense(o.reshape(B, Nq, HD), wo, self.DenseGeneral_0.bias if self.use_bias else None, dt)
-        if self.out_dropout_rate > 0.0:
-            y = F.dropout(y, p=self.out_dropout_rate, training=is_training)
-        return y
+        return attention_tail(self, q, k, v, is_training, qkv, ROTARY_BASE if self.rotary else None)
 
 
 class SelfAttentionBlock(AttentionBlock):
@@ -215,6 +208,12 @@ class LCSelfAttentionBlock(AttentionBlock):
 
 
 # ------------------------------------------------------------------ Flax param-tree interop
+def numbered(module: nn.Module, name: str):
+    """The Flax-style numbered children ``name_0, name_1, ...`` of ``module``, by number."""
+    found = ((key.rpartition("_"), m) for key, m in module.named_children())
+    return [m for _, m in sorted((int(n), m) for (stem, _, n), m in found if stem == name and n.isdigit())]
+
+
 def flax_params(module: nn.Module) -> Dict:
     """Nested dict of fp32 tensors in the reference's Flax param-tree layout
     (``{'queries': {'kernel': ...}, 'DenseGeneral_0': {...}, ...}``)."""

@@ -21,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .attention import DenseGeneral, TalkingHeadsBlock, lecun_normal_
+from .attention import DenseGeneral, TalkingHeadsBlock, attention_tail, lecun_normal_
 
 __all__ = ["ConvProjectionBlock", "CvTAttentionBlock", "CvTSelfAttentionBlock"]
 
@@ -151,30 +151,13 @@ class CvTAttentionBlock(nn.Module):
         assert in_ch % self.num_heads == 0
         if self._in_ch is None:
             self._build(in_ch, inputs_q.device)
-        drop = None   # attention-probability dropout (cvt_attention.py:100-104): inside the kernels
-        if is_training and self.attn_dropout_rate > 0.0:
-            if self.talking_heads:
-                raise NotImplementedError(
-                    "attn_dropout_rate > 0 with talking_heads=True is not implemented: the reference drops after "
-                    "the second head mix, and the talking-heads kernels have no dropout")
-            drop = (self.attn_dropout_rate, ops.dropout_rng(inputs_q.device))
-        H, D, dt = self.num_heads, self._D, self.dtype
+        H, D = self.num_heads, self._D
         q = self.ConvProjectionBlock_0(inputs_q, is_training)
         k = self.ConvProjectionBlock_1(inputs_kv, is_training)
         v = self.ConvProjectionBlock_2(inputs_kv, is_training)
         b = q.shape[0]
         q, k, v = (t.reshape(b, -1, H, D) for t in (q, k, v))          # 'b H W (h d) -> b (H W) h d'
-        scale = 1.0 / math.sqrt(D)                                      # cvt_attention.py:85
-        if self.talking_heads:
-            o = ops.talking_heads_attention(q, k, v, self.TalkingHeadsBlock_0.talking_heads_transform,
-                                            self.TalkingHeadsBlock_1.talking_heads_transform, scale)
-        else:
-            o = ops.attention(q, k, v, scale, dropout=drop)
-        y = ops.dense(o.reshape(b, -1, H * D), self.DenseGeneral_0.kernel.reshape(H * D, self._out),
-                      self.DenseGeneral_0.bias if self.use_bias else None, dt)
-        if self.out_dropout_rate > 0.0:
-            y = F.dropout(y, p=self.out_dropout_rate, training=is_training)
-        return y
+        return attention_tail(self, q, k, v, is_training)
 
 
 class CvTSelfAttentionBlock(CvTAttentionBlock):

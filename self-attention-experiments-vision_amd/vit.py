@@ -9,24 +9,26 @@ reference's mixed precision: fp32 params, ``dtype`` compute, fp32 residual strea
 cls / pos-embed params promote it, vit.py:46,85), LayerNorm eps 1e-6, tanh-GELU (Flax
 ``nn.gelu`` default).
 
-The attention is ``layers.SelfAttentionBlock`` (fused HIP kernels).  Around it (survey §8f
-"next"): Dense / DenseGeneral go through ``ops.dense`` (library GEMM forward and input gradient,
-HIP split-token weight/bias gradients), and with a bf16 compute dtype every residual add is fused
-with the LayerNorm that follows it (``ops.add_layer_norm``, HIP) and the FF block runs as
-``ops.ff_block`` (HIP GEMMs with the tanh-GELU and its derivative fused into their epilogues).
+The attention is ``layers.SelfAttentionBlock`` (fused HIP kernels); Dense / DenseGeneral go through ``ops.dense``
+(library GEMM forward and input gradient, HIP split-token weight/bias gradients).  The block is written once,
+``EncoderBlock.body``, on the stream operations of ``layers/stream.py``: every residual add is made together with the
+LayerNorm that follows it.  ``Encoder.forward`` decides the route once, on the stream that enters the first block,
+and runs one loop of bodies.  HIP route (bf16 compute): each add + LayerNorm is one kernel (``ops.add_layer_norm``),
+every Dense kernel of the encoder is cast to bf16 in one launch up front and the FF block runs as ``ops.ff_block``
+(tanh-GELU and its derivative fused into the GEMM epilogues).  Framework route: the same adds and LayerNorms as
+framework ops, in the same order.
 
-``dropout_rate`` (vit.py:12,39,68) reaches four places per training forward, each drawing one stream id
-of the device's ``ops.DropoutRng`` in this order: the encoder input after the position embedding
-(vit.py:47); then per block the attention probabilities (``attn_dropout_rate``, inside the attention
-kernels), the attention output (attention.py ``out_dropout_rate``), the FF hidden activation after
-the GELU (ff.py:30) and the FF output (ff.py:32).  In the fused bf16 encoder none of them is a pass
-of its own: the input dropout rides in ``ops.encoder_tokens``, the hidden one in the GELU GEMM's
-epilogue, the two output ones in the ``ops.add_layer_norm`` that follows; every other path applies
-``ops.dropout_rows`` at the same places with the same ids, so one seed gives one set of masks.
+``dropout_rate`` (vit.py:12,39,68) reaches four places per training forward, each drawing one stream id of the
+device's ``ops.DropoutRng`` in this order: the encoder input after the position embedding (vit.py:47); then per block
+the attention probabilities (``attn_dropout_rate``, inside the attention kernels), the attention output (attention.py
+``out_dropout_rate``), the FF hidden activation after the GELU (ff.py:30) and the FF output (ff.py:32).  On the HIP
+route none of them is a pass of its own: the input dropout rides in ``ops.encoder_tokens``, the hidden one in the GELU
+GEMM's epilogue, the two output ones in the ``ops.add_layer_norm`` that follows; the framework route applies
+``ops.dropout_rows`` at the same places.  Both routes run the one body, so one seed gives one set of masks.
 """
 from __future__ import annotations
 
-import math
+import contextlib
 from typing import Tuple
 
 import torch
@@ -34,7 +36,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .layers.attention import DenseGeneral, SelfAttentionBlock, lecun_normal_
+from .layers.attention import DenseGeneral, SelfAttentionBlock, lecun_normal_, numbered
+from .layers.stream import add_norm, fused, hidden_dropout, norm_pass
 
 __all__ = ["ViT", "create_model", "MODEL_CONFIGS", "vit_flops_per_image"]
 
@@ -66,11 +69,6 @@ class LayerNorm(nn.Module):
         return F.layer_norm(x.float(), (x.shape[-1],), self.scale, self.bias, 1e-6).to(dtype)
 
 
-def _hidden_dropout(rate: float, is_training: bool, device):
-    """``(rate, DropoutRng)`` for the ops' ``dropout=`` argument, or None (inference, rate 0)."""
-    return (rate, ops.dropout_rng(device)) if is_training and rate > 0.0 else None
-
-
 class FFBlock(nn.Module):
     """ff.py:8-34 (expand_ratio, Dense -> GELU -> Dropout -> Dense -> Dropout)."""
 
@@ -83,9 +81,9 @@ class FFBlock(nn.Module):
 
     def forward(self, x, dtype, is_training: bool = False, out_dropout: bool = True):
         """``out_dropout=False``: the caller applies the output dropout (ff.py:32) itself, inside the
-        residual add that follows (``ops.add_layer_norm(dropout=...)``)."""
+        residual add that follows (``stream.add_norm(dropout=...)``)."""
         d0, d1 = self.Dense_0, self.Dense_1
-        drop = _hidden_dropout(self.dropout_rate, is_training, x.device)
+        drop = hidden_dropout(self.dropout_rate, is_training, x.device)
         if dtype == torch.bfloat16 and ops.ff_block_ok(x, d0.kernel, d1.kernel):
             # GELU (and the hidden dropout) fused into Dense_0's GEMM epilogue, its derivative into
             # Dense_1's dX GEMM
@@ -96,7 +94,7 @@ class FFBlock(nn.Module):
 
 
 class EncoderBlock(nn.Module):
-    """vit.py:9-32."""
+    """vit.py:9-32.  ``body`` is the block; ``forward`` runs it on a stream of its own."""
 
     def __init__(self, dim, num_heads, expand_ratio, dtype, device=None, attn_dropout_rate: float = 0.0,
                  dropout_rate: float = 0.0):
@@ -104,19 +102,25 @@ class EncoderBlock(nn.Module):
         self.dtype = dtype
         self.dropout_rate = dropout_rate
         self.LayerNorm_0 = LayerNorm(dim, device)
-        # out_dropout_rate stays 0: the block owns the attention-output dropout (vit.py:22), so that
-        # the fused encoder can apply it inside the residual add
+        # out_dropout_rate stays 0: the block applies the attention-output dropout (vit.py:22) in its residual add
         self.SelfAttentionBlock_0 = SelfAttentionBlock(num_heads=num_heads, attn_dropout_rate=attn_dropout_rate,
                                                        dtype=dtype, in_ch=dim, device=device)
         self.LayerNorm_1 = LayerNorm(dim, device)
         self.FFBlock_0 = FFBlock(dim, expand_ratio, device, dropout_rate)
 
+    def body(self, x, h, next_ln, is_training, route, cls_only=False):
+        """The block on the stream ``x`` and ``h = LayerNorm_0(x)`` -> ``(x', next_ln(x'))`` (``stream.add_norm``)."""
+        drop = hidden_dropout(self.dropout_rate, is_training, x.device)
+        a = self.SelfAttentionBlock_0(h, is_training=is_training)
+        x, h = add_norm(x, a, self.LayerNorm_1, self.dtype, route, dropout=drop)
+        f = self.FFBlock_0(h, self.dtype, is_training, out_dropout=False)
+        return add_norm(x, f, next_ln, self.dtype, route, dropout=drop, cls_only=cls_only)
+
     def forward(self, inputs, is_training):
-        x = self.SelfAttentionBlock_0(self.LayerNorm_0(inputs, self.dtype), is_training=is_training)
-        x = ops.dropout_rows(x, _hidden_dropout(self.dropout_rate, is_training, x.device))
-        x = x + inputs
-        y = self.FFBlock_0(self.LayerNorm_1(x, self.dtype), self.dtype, is_training)
-        return x + y
+        """The body on the route of ``inputs``: a lone bf16 block now runs the HIP LayerNorms too, as in the encoder."""
+        route = fused(inputs, self.dtype)
+        x, h = norm_pass(inputs, self.LayerNorm_0, self.dtype, route)
+        return self.body(x, h, None, is_training, route)[0]
 
 
 def encoder_weight_groups(blocks):
@@ -127,6 +131,11 @@ def encoder_weight_groups(blocks):
         groups += blk.SelfAttentionBlock_0.weight_groups()
         groups += [[blk.FFBlock_0.Dense_0.kernel], [blk.FFBlock_0.Dense_1.kernel]]
     return groups
+
+
+def encoder_casts(blocks, route: bool):
+    """For an encoder's loop: on the HIP route every Dense kernel of ``blocks`` cast in one launch up front."""
+    return ops.forward_casts(encoder_weight_groups(blocks)) if route else contextlib.nullcontext()
 
 
 class Encoder(nn.Module):
@@ -153,35 +162,15 @@ class Encoder(nn.Module):
         x = inputs
         if not pos_added:
             x = inputs.float() + self.AddAbsPosEmbed_0.pos_embed
-            x = ops.dropout_rows(x, _hidden_dropout(self.dropout_rate, is_training, x.device))
-        blocks = [getattr(self, f"EncoderBlock_{i}") for i in range(self.num_layers)]
-        if self.dtype == torch.bfloat16 and blocks and ops.layer_norm_ok(x):
-            # Same math as vit.py:19-31,57, with every residual add fused into the LayerNorm that
-            # follows it (the next block's LayerNorm_0, or the final one): one HBM pass each; every
-            # Dense kernel of the encoder cast to bf16 in one launch up front.
-            with ops.forward_casts(encoder_weight_groups(blocks)):
-                # (x, h): the residual gradient is added inside the LayerNorm backward kernel
-                x, h = ops.layer_norm_pass(x, blocks[0].LayerNorm_0.scale, blocks[0].LayerNorm_0.bias)
-                for i, blk in enumerate(blocks):
-                    # the attention-output and FF-output dropouts ride in the residual add that follows
-                    drop = _hidden_dropout(blk.dropout_rate, is_training, x.device)
-                    a = blk.SelfAttentionBlock_0(h, is_training=is_training)
-                    x, h = ops.add_layer_norm(x, a, blk.LayerNorm_1.scale, blk.LayerNorm_1.bias, dropout=drop)
-                    f = blk.FFBlock_0(h, self.dtype, is_training, out_dropout=False)
-                    if i + 1 < len(blocks):
-                        nxt = blocks[i + 1].LayerNorm_0
-                        x, h = ops.add_layer_norm(x, f, nxt.scale, nxt.bias, dropout=drop)
-                    elif cls_only:
-                        h = ops.cls_add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias,
-                                                   dropout=drop)
-                    else:
-                        x, h = ops.add_layer_norm(x, f, self.LayerNorm_0.scale, self.LayerNorm_0.bias,
-                                                  dropout=drop)
-            return h
-        for blk in blocks:
-            x = blk(x, is_training)
-        y = self.LayerNorm_0(x, self.dtype)
-        return y[:, 0] if cls_only else y
+            x = ops.dropout_rows(x, hidden_dropout(self.dropout_rate, is_training, x.device))
+        blocks = numbered(self, "EncoderBlock")
+        route = bool(blocks) and fused(x, self.dtype)   # decided on the first block's input, and held
+        lns = [blk.LayerNorm_0 for blk in blocks] + [self.LayerNorm_0]   # lns[i + 1] reads block i's output
+        with encoder_casts(blocks, route):
+            x, h = norm_pass(x, lns[0], self.dtype, route)
+            for blk, ln in zip(blocks, lns[1:]):
+                x, h = blk.body(x, h, ln, is_training, route, cls_only and ln is lns[-1])
+        return h[:, 0] if cls_only and not blocks else h
 
 
 def patch_tokens(pe: nn.Module, inputs: torch.Tensor, patch_shape: Tuple[int, int], dtype: torch.dtype,
@@ -228,9 +217,8 @@ class ViT(nn.Module):
         (FusedAdamW ``cast_groups``).  None when the model computes in fp32."""
         if self.dtype != torch.bfloat16:
             return None
-        blocks = [getattr(self.Encoder_0, f"EncoderBlock_{i}") for i in range(self.Encoder_0.num_layers)]
-        return (encoder_weight_groups(blocks) + [[self.PatchEmbedBlock_0.Dense_0.kernel]] +
-                [[self.Dense_0.kernel]])
+        return (encoder_weight_groups(numbered(self.Encoder_0, "EncoderBlock")) +
+                [[self.PatchEmbedBlock_0.Dense_0.kernel]] + [[self.Dense_0.kernel]])
 
     def forward(self, inputs: torch.Tensor, is_training: bool, layout: str = "NHWC") -> torch.Tensor:
         """``layout`` "HWCN": ``inputs`` is the train-step feed [H, W, C, B] (train.py:80)."""
@@ -239,7 +227,7 @@ class ViT(nn.Module):
         pos = self.Encoder_0.AddAbsPosEmbed_0.pos_embed
         if self.dtype == torch.bfloat16 and ops.encoder_tokens_ok(x, self.cls, pos):
             # concat(cls, tokens) + pos_embed (and the input dropout) into the fp32 residual stream in one pass
-            drop = _hidden_dropout(self.dropout_rate, is_training, x.device)
+            drop = hidden_dropout(self.dropout_rate, is_training, x.device)
             x = self.Encoder_0(ops.encoder_tokens(x, self.cls, pos, dropout=drop), is_training, pos_added=True,
                                cls_only=True)
         else:
