@@ -466,6 +466,40 @@ int sae_dwconv_bn_bwd(void* stream, const sae_dwconv_desc* desc, const void* x, 
                       const float* gamma, const void* t, const float* mean, const float* rstd,
                       const void* dy, void* dx, float* dw, float* dgamma, float* dbeta, void* workspace);
 
+/* ---- BatchNorm over token rows + tanh-GELU (CeiT LeFF, models/layers/feedforwards/leff.py:39-59) ----
+   x [B][L + x_lead][C] in the compute dtype; x_lead (0 or 1) leading rows per sample (the class
+   token) are skipped and N = B L rows take part.  y [B][L + y_lead][C]; with y_lead = 1 row 0 of
+   every sample of y is a copy of the row of C elements at lead + b * lead_pitch (elements).
+     training:   mu, var = biased batch statistics per channel (fp64 sums), r = rsqrt(var + eps),
+                 z = T(((x - mu) r) gamma + beta), y = T(gelu(z)) (tanh form); mean = mu and rstd = r are
+                 saved; run_mean = m run_mean + (1 - m) mu, run_var likewise, on the device in stream order
+     evaluation: the same formula with run_mean / run_var; buffers untouched, mean / rstd / workspace unused
+   gamma, beta, run_mean, run_var, mean, rstd fp32 [C].  channels must be a multiple of 8 (bf16) or 4
+   (fp32), lead_pitch a multiple of the same, every pointer 16-byte aligned and B (L + 1) C <= 2^31 - 1;
+   anything else is SAE_EUNSUPPORTED.  Fixed-order reductions (no atomics): two calls on the same inputs
+   agree bit for bit.  No host synchronisation. */
+typedef struct sae_bnrows_desc {
+  int32_t batch, tokens, channels;
+  int32_t x_lead, y_lead; /* 0 or 1 */
+  int32_t dtype;          /* SAE_DTYPE_* */
+  int32_t training;       /* 0: evaluation (running statistics), else batch statistics */
+  float momentum;         /* of the running averages (Flax convention) */
+  float eps;
+} sae_bnrows_desc;
+/* Bytes sae_bn_gelu_fwd / _bwd need at `workspace` for either compute dtype (0: unsupported shape). */
+size_t sae_bn_gelu_workspace_bytes(int32_t B, int32_t L, int32_t C);
+int sae_bn_gelu_fwd(void* stream, const sae_bnrows_desc* desc, const void* x, const float* gamma,
+                    const float* beta, float* run_mean, float* run_var, const void* lead, int64_t lead_pitch,
+                    void* y, float* mean, float* rstd, void* workspace);
+/* Backward of the training form from x, the saved mean / rstd and g = dy (y's layout): z is recomputed
+   with the forward's rounding, dz = g gelu'(z), dbeta = sum dz, dgamma = sum dz xhat,
+   dx = T(gamma r (dz - dbeta / N - xhat dgamma / N)) in x's layout with the skipped lead rows written
+   as zeros.  The gradient of `lead` is row 0 of every sample of dy.  dgamma, dbeta are overwritten.
+   desc->training == 0 is SAE_EUNSUPPORTED. */
+int sae_bn_gelu_bwd(void* stream, const sae_bnrows_desc* desc, const void* x, const float* gamma,
+                    const float* beta, const float* mean, const float* rstd, const void* dy, void* dx,
+                    float* dgamma, float* dbeta, void* workspace);
+
 /* The CvT convolutional token embedding (models/cvt.py:19-35): a dense kernel x kernel convolution
    with stride < kernel and Flax SAME padding (Ho = ceil(H / stride), total padding
    max((Ho - 1) stride + kernel - H, 0), the smaller half in front), as a window matrix written once

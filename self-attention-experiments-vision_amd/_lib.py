@@ -57,6 +57,12 @@ class SaeDwconvDesc(ctypes.Structure):
                 ("dtype", _i32), ("training", _i32), ("momentum", _f32), ("eps", _f32)]
 
 
+class SaeBnrowsDesc(ctypes.Structure):
+    """Mirror of ``sae_bnrows_desc`` (include/sae_attn.h)."""
+    _fields_ = [("batch", _i32), ("tokens", _i32), ("channels", _i32), ("x_lead", _i32), ("y_lead", _i32),
+                ("dtype", _i32), ("training", _i32), ("momentum", _f32), ("eps", _f32)]
+
+
 class SaeConvtokDesc(ctypes.Structure):
     """Mirror of ``sae_convtok_desc`` (include/sae_attn.h)."""
     _fields_ = [("batch", _i32), ("height", _i32), ("width", _i32), ("channels", _i32), ("kernel", _i32),
@@ -71,6 +77,9 @@ _PROTOS = [
     ("sae_dwconv_bn_workspace_bytes", _sz, [_i32] * 5),
     ("sae_dwconv_bn_fwd", _i32, [_vp, ctypes.POINTER(SaeDwconvDesc)] + [_vp] * 11),
     ("sae_dwconv_bn_bwd", _i32, [_vp, ctypes.POINTER(SaeDwconvDesc)] + [_vp] * 12),
+    ("sae_bn_gelu_workspace_bytes", _sz, [_i32] * 3),
+    ("sae_bn_gelu_fwd", _i32, [_vp, ctypes.POINTER(SaeBnrowsDesc)] + [_vp] * 6 + [_i64] + [_vp] * 4),
+    ("sae_bn_gelu_bwd", _i32, [_vp, ctypes.POINTER(SaeBnrowsDesc)] + [_vp] * 10),
     ("sae_attn_desc_init", None, [ctypes.POINTER(SaeAttnDesc), _i32, _i32, _i32, _i32, _i32, _i32, _f32]),
     ("sae_attn_fwd", _i32, [_vp, ctypes.POINTER(SaeAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("sae_attn_bwd_workspace_bytes", _sz, [ctypes.POINTER(SaeAttnDesc)]),

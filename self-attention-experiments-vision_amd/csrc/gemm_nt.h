@@ -32,6 +32,7 @@
 #pragma once
 #include "common.h"
 #include "drop_rows.h"
+#include "gelu.h"
 
 namespace sae {
 
@@ -56,21 +57,7 @@ struct NtArgs {
 constexpr int kNtT = 128;   // output tile edge
 constexpr int kNtK = 64;    // K per stage
 
-// tanh-GELU (Flax nn.gelu default; torch approximate="tanh"): 0.5 x (1 + tanh(y)),
-// y = sqrt(2/pi) (x + 0.044715 x^3) = x * sigmoid(2y)
-constexpr float kGeluB = 0.7978845608028654f;
-constexpr float kGeluK = 0.044715f;
-
-__device__ __forceinline__ float gelu_sig(float x) {   // sigmoid(2y)
-  const float y2 = x * (kGeluB + (kGeluB * kGeluK) * x * x);
-  return __builtin_amdgcn_rcpf(1.f + ex2(-2.f * kLog2e * y2));
-}
-__device__ __forceinline__ float gelu_f(float x) { return x * gelu_sig(x); }
-__device__ __forceinline__ float dgelu_f(float x) {
-  const float s = gelu_sig(x);
-  return s + 2.f * x * s * (1.f - s) * (kGeluB + (3.f * kGeluB * kGeluK) * x * x);
-}
-
+// The scalar tanh-GELU (gelu_f, dgelu_f and their constants) is in gelu.h.
 // The epilogues on pairs of elements: the polynomial / sigmoid algebra in packed f32
 // (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two elements per VALU issue), the two
 // transcendentals per element scalar.  A bf16 pair is one 32-bit word: lo = w << 16, hi = w & ~0xffff.

@@ -2,10 +2,11 @@
 // (tokens.h), the hidden-state dropout of row-major activations (drop_rows.h: their dropout forms
 // and the standalone kernels), the cross-entropy family (label-smoothed, mixup / cutmix targets, top-k)
 // and the evaluation accumulator (loss.h), AdamW (adamw.h), the CvT convolutional projection
-// (depthwise 3x3 + BatchNorm, dwconv.h), the CvT convolutional token embedding's window matrix
-// (convtok.h), the stream utilities of bench.py, and the library's error string and version.
+// (depthwise 3x3 + BatchNorm, dwconv.h), the CeiT LeFF block's BatchNorm + GELU over token rows
+// (bn_rows.h), the CvT convolutional token embedding's window matrix (convtok.h), the stream utilities of bench.py, and the library's error string and version.
 #include "ln.h"
 #include "dwconv.h"
+#include "bn_rows.h"
 #include "convtok.h"
 #include "loss.h"
 #include "tokens.h"
@@ -375,6 +376,107 @@ int dw_bwd_launch(hipStream_t st, const sae_dwconv_desc& d, DwConvArgs& a) {
 }
 
 
+// ------------------------------------------------- BatchNorm + GELU over token rows (CeiT LeFF)
+// The launch geometry of bn_rows.h for one element type.  A workgroup's 256 threads are PS row slots
+// x CVt channel vectors; the C / V channel vectors are cut into `chunks` equal runs of CVt >= 8
+// vectors (128-byte runs of a row) so that PS CVt comes closest to 256 live threads (C = 768 in
+// bf16: 3 chunks of 32 vectors x 8 slots, not 96 vectors x 2 slots with 64 threads idle).  The
+// statistics grids are capped like the dw pass of the depthwise convolution: their fp64 partial
+// rows (16 bytes per channel and workgroup) stay near 4 MB.
+struct BnGrid {
+  int chunks, sums, apply, dx;
+};
+
+BnGrid bn_geometry(const sae_bnrows_desc& d, int V, DwConvArgs& a, BnRows& r) {
+  a.C = d.channels;
+  const int CV = a.C / V;
+  int best = 0, chunks = 1;
+  for (int n = (CV + 255) / 256; n <= CV; ++n) {
+    const int cvt = (CV + n - 1) / n;
+    if (cvt < 8 && n > (CV + 255) / 256) break;
+    const int live = 256 / cvt * CV;   // live threads of the n workgroups of one row-slot set
+    if (live * chunks > best * n) {    // live / n > best / chunks
+      best = live;
+      chunks = n;
+    }
+  }
+  a.CVt = (CV + chunks - 1) / chunks;
+  a.PS = 256 / a.CVt;
+  a.npix = (long long)d.batch * d.tokens;
+  a.momentum = d.momentum;
+  a.eps = d.eps;
+  r.L = d.tokens;
+  r.x_lead = d.x_lead;
+  r.y_lead = d.y_lead;
+  r.rows_x = d.batch * (d.tokens + d.x_lead);
+  r.rows_y = d.batch * (d.tokens + d.y_lead);
+  r.dL = FDiv::make((unsigned)r.L);
+  r.dLx = FDiv::make((unsigned)(r.L + r.x_lead));
+  r.dLy = FDiv::make((unsigned)(r.L + r.y_lead));
+  BnGrid g;
+  g.chunks = chunks;
+  g.sums = dw_blocks(a.npix, a.PS * kDwPix, std::max(128, std::min(kDwMaxBlocks, (4 << 20) / (16 * a.C))));
+  g.apply = dw_blocks(r.rows_y, a.PS * kDwPix, 2 * kDwMaxBlocks);
+  g.dx = dw_blocks(r.rows_x, a.PS * kDwPix, 2 * kDwMaxBlocks);
+  return g;
+}
+
+size_t bn_workspace(int32_t B, int32_t L, int32_t C, int V) {
+  sae_bnrows_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = B;
+  d.tokens = L;
+  d.channels = C;
+  DwConvArgs a;
+  BnRows r;
+  return (size_t)bn_geometry(d, V, a, r).sums * 2 * C * sizeof(double);
+}
+
+// element offsets of x, y and lead rows must fit 31 bits (one more row per sample than tokens)
+bool bn_extent_ok(long long B, long long L, long long C) { return B * (L + 1) * C <= 0x7fffffffLL; }
+
+// everything but the pointers; every refusal returns before any HIP call
+int bn_check(const char* what, const sae_bnrows_desc* d) {
+  if (!d) return fail(SAE_EINVAL, "%s: NULL descriptor", what);
+  if (d->batch < 1 || d->tokens < 1 || d->channels < 1)
+    return fail(SAE_EUNSUPPORTED, "%s: batch %d, tokens %d, channels %d must be >= 1", what, d->batch, d->tokens, d->channels);
+  if (d->dtype != SAE_DTYPE_BF16 && d->dtype != SAE_DTYPE_F32) return fail(SAE_EINVAL, "%s: bad dtype %d", what, d->dtype);
+  if ((d->x_lead != 0 && d->x_lead != 1) || (d->y_lead != 0 && d->y_lead != 1))
+    return fail(SAE_EINVAL, "%s: x_lead %d, y_lead %d (0 or 1)", what, d->x_lead, d->y_lead);
+  const int V = d->dtype == SAE_DTYPE_BF16 ? 8 : 4;
+  if (d->channels % V)
+    return fail(SAE_EUNSUPPORTED, "%s: channels %d must be a multiple of %d in %s", what, d->channels, V,
+                d->dtype == SAE_DTYPE_BF16 ? "bf16" : "fp32");
+  if (!bn_extent_ok(d->batch, d->tokens, d->channels))
+    return fail(SAE_EUNSUPPORTED, "%s: element offsets exceed 2^31 - 1 (batch * (tokens + 1) * channels)", what);
+  return SAE_OK;
+}
+
+template <typename T>
+int bn_fwd_launch(hipStream_t st, const sae_bnrows_desc& d, DwConvArgs& a, BnRows& r) {
+  const BnGrid g = bn_geometry(d, DwVec<T>::N, a, r);
+  const dim3 gs((unsigned)g.sums, (unsigned)g.chunks), ga((unsigned)g.apply, (unsigned)g.chunks);
+  if (!d.training) return launch("bn_gelu_eval", bn_rows_apply_kernel<T, false>, ga, dim3(256), 0, st, a, r);
+  a.nparts = g.sums;
+  if (int rc = launch("bn_gelu_stats", bn_rows_stats_kernel<T>, gs, dim3(256), 0, st, a, r)) return rc;
+  if (int rc = launch("bn_gelu_stats_reduce", dwconv_reduce_kernel<double, true>, (long long)(a.C + kDwRedC - 1) / kDwRedC,
+                      dim3(256), 0, st, a, a.C, (float*)nullptr, (float*)nullptr, 0))
+    return rc;
+  return launch("bn_gelu_apply", bn_rows_apply_kernel<T, true>, ga, dim3(256), 0, st, a, r);
+}
+
+template <typename T>
+int bn_bwd_launch(hipStream_t st, const sae_bnrows_desc& d, DwConvArgs& a, BnRows& r) {
+  const BnGrid g = bn_geometry(d, DwVec<T>::N, a, r);
+  const dim3 gs((unsigned)g.sums, (unsigned)g.chunks), gx((unsigned)g.dx, (unsigned)g.chunks);
+  a.nparts = g.sums;
+  if (int rc = launch("bn_gelu_bwd_sums", bn_rows_bwd_sums_kernel<T>, gs, dim3(256), 0, st, a, r)) return rc;
+  if (int rc = launch("bn_gelu_bwd_sums_reduce", dwconv_reduce_kernel<double, false>,
+                      (long long)(2 * a.C + kDwRedC - 1) / kDwRedC, dim3(256), 0, st, a, 2 * a.C, a.dbeta, a.dgamma, a.C))
+    return rc;
+  return launch("bn_gelu_dx", bn_rows_dx_kernel<T>, gx, dim3(256), 0, st, a, r);
+}
+
 // ------------------------------------------- window matrix of the conv token embedding (CvT)
 // Everything but the pointers, and the geometry of convtok.h; every refusal returns before any HIP
 // call.  `gather`: in_dtype is read (the scatter has no x).
@@ -681,6 +783,81 @@ int sae_dwconv_bn_bwd(void* stream, const sae_dwconv_desc* desc, const void* x, 
   a.part = workspace;
   return by_dtype(desc->dtype, [&](auto* p) {
     return dw_bwd_launch<std::remove_pointer_t<decltype(p)>>((hipStream_t)stream, *desc, a);
+  });
+}
+
+// ------------------------------------------------- BatchNorm + GELU over token rows (CeiT LeFF)
+size_t sae_bn_gelu_workspace_bytes(int32_t B, int32_t L, int32_t C) {
+  if (B < 1 || L < 1 || C < 1 || C % 4 || !bn_extent_ok(B, L, C)) return 0;
+  return std::max(bn_workspace(B, L, C, 4), C % 8 ? (size_t)0 : bn_workspace(B, L, C, 8));   // either element type
+}
+
+int sae_bn_gelu_fwd(void* stream, const sae_bnrows_desc* desc, const void* x, const float* gamma, const float* beta,
+                    float* run_mean, float* run_var, const void* lead, int64_t lead_pitch, void* y, float* mean,
+                    float* rstd, void* workspace) {
+  if (int rc = bn_check("bn_gelu_fwd", desc)) return rc;
+  if (!x || !gamma || !beta || !run_mean || !run_var || !y)
+    return fail(SAE_EINVAL, "bn_gelu_fwd: NULL x / gamma / beta / run_mean / run_var / y");
+  if (desc->training && (!mean || !rstd || !workspace))
+    return fail(SAE_EINVAL, "bn_gelu_fwd: training needs mean, rstd and workspace");
+  const int V = desc->dtype == SAE_DTYPE_BF16 ? 8 : 4;
+  if (desc->y_lead) {
+    if (!lead) return fail(SAE_EINVAL, "bn_gelu_fwd: y_lead = 1 needs lead");
+    if (lead_pitch < 0 || lead_pitch % V)
+      return fail(SAE_EUNSUPPORTED, "bn_gelu_fwd: lead_pitch %lld must be a non-negative multiple of %d", (long long)lead_pitch, V);
+    if ((long long)(desc->batch - 1) * lead_pitch + desc->channels > 0x7fffffffLL)
+      return fail(SAE_EUNSUPPORTED, "bn_gelu_fwd: lead element offsets exceed 2^31 - 1");
+  }
+  if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(run_mean) || !aligned16(run_var) ||
+      !aligned16(lead) || !aligned16(y) || !aligned16(mean) || !aligned16(rstd) || !aligned16(workspace))
+    return fail(SAE_EUNSUPPORTED, "bn_gelu_fwd: every pointer needs 16-byte alignment");
+  DwConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.run_mean = run_mean;
+  a.run_var = run_var;
+  a.y = y;
+  a.mean = mean;
+  a.rstd = rstd;
+  a.part = workspace;
+  BnRows r;
+  memset(&r, 0, sizeof r);
+  r.lead = desc->y_lead ? lead : x;   // (never read without y_lead)
+  r.lead_pitch = desc->y_lead ? lead_pitch : 0;
+  return by_dtype(desc->dtype, [&](auto* p) {
+    return bn_fwd_launch<std::remove_pointer_t<decltype(p)>>((hipStream_t)stream, *desc, a, r);
+  });
+}
+
+int sae_bn_gelu_bwd(void* stream, const sae_bnrows_desc* desc, const void* x, const float* gamma, const float* beta,
+                    const float* mean, const float* rstd, const void* dy, void* dx, float* dgamma, float* dbeta,
+                    void* workspace) {
+  if (int rc = bn_check("bn_gelu_bwd", desc)) return rc;
+  if (!desc->training)
+    return fail(SAE_EUNSUPPORTED, "bn_gelu_bwd: training = 0 (the evaluation form has no backward)");
+  if (!x || !gamma || !beta || !mean || !rstd || !dy || !dx || !dgamma || !dbeta || !workspace)
+    return fail(SAE_EINVAL, "bn_gelu_bwd: NULL argument");
+  if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(mean) || !aligned16(rstd) || !aligned16(dy) ||
+      !aligned16(dx) || !aligned16(dgamma) || !aligned16(dbeta) || !aligned16(workspace))
+    return fail(SAE_EUNSUPPORTED, "bn_gelu_bwd: every pointer needs 16-byte alignment");
+  DwConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = x;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.mean = const_cast<float*>(mean);
+  a.rstd = const_cast<float*>(rstd);
+  a.dy = dy;
+  a.dx = dx;
+  a.dgamma = dgamma;
+  a.dbeta = dbeta;
+  a.part = workspace;
+  BnRows r;
+  memset(&r, 0, sizeof r);
+  return by_dtype(desc->dtype, [&](auto* p) {
+    return bn_bwd_launch<std::remove_pointer_t<decltype(p)>>((hipStream_t)stream, *desc, a, r);
   });
 }
 

@@ -3,9 +3,10 @@ from .attention import (AttentionBlock, ClassSelfAttentionBlock, DenseGeneral, L
                         SelfAttentionBlock, TalkingHeadsBlock, flax_params, load_flax_params)
 from .botnet import BoTMHSA, RelativeLogits
 from .cvt import ConvProjectionBlock, CvTAttentionBlock, CvTSelfAttentionBlock
+from .leff import LeFFBlock
 from .position_embed import RotaryPositionalEmbedding
 
 __all__ = ["AttentionBlock", "SelfAttentionBlock", "TalkingHeadsBlock", "ClassSelfAttentionBlock",
            "LCSelfAttentionBlock", "DenseGeneral", "RelativeLogits", "BoTMHSA",
            "RotaryPositionalEmbedding", "ConvProjectionBlock", "CvTAttentionBlock", "CvTSelfAttentionBlock",
-           "flax_params", "load_flax_params"]
+           "LeFFBlock", "flax_params", "load_flax_params"]

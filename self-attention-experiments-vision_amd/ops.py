@@ -31,7 +31,7 @@ __all__ = ["attention", "attention_packed", "dense", "ff_block", "gemm_nt", "wei
            "relpos_bias", "rotary", "rotary_tables", "dtype_code", "KernelTimer", "set_kernel_timer",
            "DenseFacts", "dense_facts_of_shapes", "dense_fwd_plan", "dense_bwd_plan",
            "dwconv_bn", "dwconv_bn_ok", "same_pads", "conv_tokens", "conv_tokens_ok", "conv_window_matrix",
-           "conv_window_scatter", "conv_window_cols"]
+           "conv_window_scatter", "conv_window_cols", "bn_gelu", "bn_gelu_ok"]
 
 
 class KernelTimer:
@@ -1870,6 +1870,121 @@ def dwconv_bn(x: torch.Tensor, w: torch.Tensor, gamma: torch.Tensor, beta: torch
     x = x if x.is_contiguous() else x.contiguous()
     return _DwConvBn.apply(x, _f32c(w), _f32c(gamma), _f32c(beta), run_mean, run_var, int(stride),
                            float(momentum), float(eps), bool(training))
+
+
+# ------------------------------------------- CeiT LeFF: BatchNorm over token rows + tanh-GELU
+def bn_gelu_ok(x, dtype: torch.dtype, training: bool = True, needs_grad: Optional[bool] = None,
+               x_lead: int = 0) -> bool:
+    """Host predicate of :func:`bn_gelu` (``sae_bn_gelu_*``): a GPU tensor [B, L + x_lead, C] with
+    B, L >= 1, bf16 with C % 8 == 0 or fp32 with C % 4 == 0, and B (L + 1) C < 2^31 (element offsets of
+    either layout fit 31 bits).  The evaluation form has no backward: with a gradient wanted
+    (``needs_grad``; default: ``x.requires_grad`` under grad mode) it is not taken."""
+    if not getattr(x, "is_cuda", False) or len(x.shape) != 3 or x_lead not in (0, 1):
+        return False
+    if dtype not in (torch.bfloat16, torch.float32):
+        return False
+    B, R, C = x.shape
+    if B < 1 or R - x_lead < 1 or C < 1 or C % (8 if dtype == torch.bfloat16 else 4):
+        return False
+    if B * (R - x_lead + 1) * C >= 2 ** 31:
+        return False
+    if needs_grad is None:
+        needs_grad = torch.is_grad_enabled() and bool(x.requires_grad)
+    return bool(training) or not needs_grad
+
+
+def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as a contiguous, 16-byte-aligned tensor (itself when it already is one)."""
+    if not t.is_contiguous():
+        t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _BnGelu(torch.autograd.Function):
+    """``sae_bn_gelu_fwd`` / ``_bwd``: saves x and the batch mean / rstd, nothing else (z is recomputed);
+    the running buffers are advanced by the forward's kernels (stream-ordered, no host read)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, lead, run_mean, run_var, momentum, eps, training, x_lead, y_lead):
+        lib = L.load()
+        B, R, C = x.shape
+        Lt = R - x_lead
+        d = L.SaeBnrowsDesc(B, Lt, C, x_lead, y_lead, dtype_code(x.dtype), 1 if training else 0, float(momentum),
+                            float(eps))
+        y = torch.empty((B, Lt + y_lead, C), dtype=x.dtype, device=x.device)
+        mean = rstd = ws = None
+        if training:
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.sae_bn_gelu_workspace_bytes(B, Lt, C), dtype=torch.uint8, device=x.device)
+        tok = _TIMER.begin("bn_gelu_fwd") if _TIMER is not None else None
+        L.check(lib.sae_bn_gelu_fwd(_stream(x), ctypes.byref(d), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(run_mean),
+                                    _ptr(run_var), _ptr(lead), lead.stride(0) if lead is not None else 0, _ptr(y),
+                                    _ptr(mean), _ptr(rstd), _ptr(ws)))
+        if tok is not None:
+            _TIMER.end(tok, (B, Lt, C, x_lead, y_lead))
+        ctx.training = training
+        if training:
+            ctx.save_for_backward(x, gamma, beta, mean, rstd)
+            ctx.desc = d
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.training:
+            raise RuntimeError("bn_gelu: the evaluation form has no backward (bn_gelu_ok refuses it)")
+        lib = L.load()
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        d = ctx.desc
+        B, _, C = x.shape
+        dy = _aligned_rows(dy.to(x.dtype))
+        dx = torch.empty_like(x)   # (its skipped lead rows are written as zeros by the kernel)
+        dg = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.sae_bn_gelu_workspace_bytes(B, d.tokens, C), dtype=torch.uint8, device=x.device)
+        tok = _TIMER.begin("bn_gelu_bwd") if _TIMER is not None else None
+        L.check(lib.sae_bn_gelu_bwd(_stream(x), ctypes.byref(d), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean),
+                                    _ptr(rstd), _ptr(dy), _ptr(dx), _ptr(dg), _ptr(db), _ptr(ws)))
+        if tok is not None:
+            _TIMER.end(tok, (B, d.tokens, C, d.x_lead, d.y_lead))
+        dlead = dy[:, :1] if d.y_lead and ctx.needs_input_grad[3] else None   # a view: no kernel
+        return dx, dg, db, dlead, None, None, None, None, None, None, None
+
+
+def bn_gelu(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, run_mean: torch.Tensor, run_var: torch.Tensor,
+            momentum: float, eps: float, training: bool, dtype: torch.dtype, x_lead: int = 0, y_lead: int = 0,
+            lead: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """BatchNorm over the token rows followed by the tanh-GELU (leff.py:40-41, 52-53, 58-59) of ``x``
+    [B, L + x_lead, C] in the compute dtype ``dtype`` -> [B, L + y_lead, C].  ``x_lead`` (0 or 1)
+    leading rows per sample -- the class token -- take no part and are not read; with ``y_lead = 1``
+    row 0 of every sample of the output is ``lead`` ([B, 1, C] or [B, C], e.g. ``inputs[:, :1]``: a view
+    is read in place through its sample stride), so the last BatchNorm of the block writes the
+    concatenated output.  ``gamma`` / ``beta`` are the BatchNorm scale / bias, ``run_mean`` /
+    ``run_var`` its fp32 batch_stats buffers: training normalises with the biased batch statistics and
+    moves the buffers in place (ra = momentum * ra + (1 - momentum) * batch), evaluation reads them.
+    Gradients of x (zero in its lead rows), gamma, beta and lead.  No host synchronisation: the call
+    can be captured into a graph."""
+    _require_gpu(x, gamma, beta, run_mean, run_var, lead)
+    x_lead, y_lead = int(x_lead), int(y_lead)
+    if not bn_gelu_ok(x, dtype, x_lead=x_lead) or y_lead not in (0, 1):
+        raise ValueError(f"bn_gelu: unsupported call (x {tuple(x.shape)}, x_lead {x_lead}, y_lead {y_lead}, {dtype}); "
+                         "see bn_gelu_ok")
+    if run_mean.dtype != torch.float32 or run_var.dtype != torch.float32 or not run_mean.is_contiguous() \
+            or not run_var.is_contiguous():
+        raise ValueError("bn_gelu: run_mean / run_var must be contiguous fp32 buffers (they are updated in place)")
+    B, _, C = x.shape
+    if (lead is not None) != bool(y_lead):
+        raise ValueError("bn_gelu: lead is given exactly when y_lead = 1")
+    if lead is not None:
+        if tuple(lead.shape) not in ((B, 1, C), (B, C)):
+            raise ValueError(f"bn_gelu: lead must be [{B}, 1, {C}] or [{B}, {C}], got {tuple(lead.shape)}")
+        lead = lead.to(dtype).reshape(B, 1, C) if lead.dim() == 2 else lead.to(dtype)
+        V = 8 if dtype == torch.bfloat16 else 4
+        if lead.stride(2) != 1 or lead.stride(0) % V or lead.data_ptr() % 16:
+            lead = _aligned_rows(lead)
+    x = _aligned_rows(x.to(dtype))
+    return _BnGelu.apply(x, _f32c(gamma), _f32c(beta), lead, run_mean, run_var, float(momentum), float(eps),
+                         bool(training), x_lead, y_lead)
 
 
 # --------------------------------------------- CvT token embedding: k x k convolution, stride < k
